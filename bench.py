@@ -16,8 +16,16 @@ which every env sits in the same phase would time only that phase; the
 `period` leg times 1 000 consecutive launches of phase-aligned envs instead).
 
 Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--envs E]
+                       [--dump-outputs DIR] [--full]
        (N>1: python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...)
 Prints ONE JSON line on rank 0.
+
+A plain run does what the headline figure needs: set up, fast-forward, warm up,
+time the K steps, write the outputs (--dump-outputs) and print the line. Every
+other leg (external actions, fused rollout, replica reduction, parity against
+the C oracle, CPU baselines, period / nominal-load / PPO / stress legs) runs
+under --full only, after the headline window, and is reported in the same line
+(VMP_BENCH_FULL=1 in the environment turns --full on by default).
 """
 import argparse
 import ctypes
@@ -98,6 +106,21 @@ def main():
     ap.add_argument("--ext-steps", type=int, default=50, help="external-action leg steps")
     ap.add_argument("--stress-ff", type=int, default=2000, help="C5 fast-forward (2*L)")
     ap.add_argument("--stress-steps", type=int, default=20)
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned as "
+                         "DIR/<name>.npy: obs (f32, a fixed seeded sample of env rows within "
+                         f"{DUMP_OBS_BYTES >> 20} MiB, the row indices in obs_rows as f64), reward (f64), "
+                         "done (f32)")
+    ap.add_argument("--full", action="store_true",
+                    default=os.environ.get("VMP_BENCH_FULL", "0") not in ("", "0"),
+                    help="(default on when the environment has VMP_BENCH_FULL=1, for scripts "
+                         "that run several bench lines) "
+                         "also run every leg beside the headline: external actions, fused "
+                         "rollout, replicas, parity vs the C oracle, CPU baselines, period, "
+                         "nominal load, PPO train / eval, stress. The options that size or "
+                         "skip those legs (--no-cpu, --cpu-threads, --no-ppo, --ppo-*, "
+                         "--ext-steps, --period-* except --period-only, --nominal-steps, "
+                         "--stress-*) have no effect without it")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -187,6 +210,91 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed, kern_ms = float(t[0]), float(t[1])
     value = world * N * K / elapsed
+    if args.dump_outputs:  # before any other leg steps the envs on
+        dump_outputs(args.dump_outputs, rank, obs, rew, done)
+
+    out = {
+        "metric": METRIC, "value": value, "unit": "env-steps/s", "n_gpus": world, "steps": K,
+        "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / K, "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+        "config": {"workload": "config/100.yml with vms=1000 (P100 V1000), FirstFit act + "
+                               "VmEnv.step fused, one launch per step", "envs_per_gpu": N,
+                   "global_envs": world * N, "pms": P, "vms": V,
+                   "arrival_rate": CFG["arrival_rate"], "service_length": CFG["service_length"],
+                   "reward_function": "wr", "policy": "firstfit", "mode": "train",
+                   "parallelism": f"env-shard x{world}", "steady_state_ff_steps": args.ff_steps,
+                   "phase_stagger": f"{args.phase_groups} groups x {args.phase_delta} steps: "
+                                    f"env ages {ff_total - (args.phase_groups - 1) * args.phase_delta}"
+                                    f"-{ff_total} at the window"},
+        "roofline": headline_roofline(P, V, N, words, pmw, kern_ms),
+        "full": bool(args.full),
+    }
+    if args.full:
+        out.update(full_legs(args, env, dev, stream, dist, world, rank, seeds, reset_at,
+                             ff_total, K))
+    else:
+        env.close()
+    if rank == 0:
+        print(json.dumps(out), flush=True)
+    if dist:
+        dist.destroy_process_group()
+
+
+DUMP_OBS_BYTES = 32 << 20  # obs sample budget of --dump-outputs (64 MB allowed in all)
+
+
+def dump_outputs(path, rank, obs, rew, done):
+    """--dump-outputs: the arrays the last timed vmp_heuristic_step returned
+    (obs f32[N, D], reward f64[N], done u8[N]). obs is sampled by env row: a
+    fixed seeded choice of as many rows as fit DUMP_OBS_BYTES (all of them when
+    they fit), the same rows in every run of the same --envs; reward and done
+    are written whole (done as f32). Rank r > 0 writes <name>_rank<r>.npy."""
+    os.makedirs(path, exist_ok=True)
+    N, D = obs.shape
+    rows = np.arange(N)
+    keep = max(1, DUMP_OBS_BYTES // (4 * D))
+    if keep < N:
+        rows = np.sort(np.random.default_rng(0).choice(N, size=keep, replace=False))
+    sfx = f"_rank{rank}" if rank else ""
+    idx = torch.from_numpy(rows).to(obs.device)
+    np.save(os.path.join(path, f"obs{sfx}.npy"), obs[idx].cpu().numpy().astype(np.float32))
+    np.save(os.path.join(path, f"obs_rows{sfx}.npy"), rows.astype(np.float64))
+    np.save(os.path.join(path, f"reward{sfx}.npy"), rew.cpu().numpy().astype(np.float64))
+    np.save(os.path.join(path, f"done{sfx}.npy"), done.cpu().numpy().astype(np.float32))
+
+
+def headline_roofline(P, V, N, words, pmw, kern_ms):
+    """HBM roofline of the timed window itself (algorithmic bytes over the
+    event-bracketed launch time), beside the committed PMC pass's traffic and
+    issue figures when profiles/traffic.json matches this --envs."""
+    bpe = step_bytes(P, V, words, pmw)
+    achieved = bpe * N / (kern_ms * 1e-3) / 1e9
+    traffic = None
+    issue = None
+    tpath = os.path.join(ROOT, "profiles", "traffic.json")
+    if os.path.exists(tpath):
+        try:
+            tj = json.load(open(tpath))
+            if tj.get("envs") == N and tj.get("bytes_per_launch"):
+                traffic = float(tj["bytes_per_launch"])
+            if tj.get("envs") == N and tj.get("SQ_INSTS_VALU"):
+                issue = issue_roofline(tj, N, kern_ms)
+        except Exception:
+            traffic = None
+    return {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+            "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
+            "kernel": "vmp::k_env<16, true> (heuristic act+step, one step per launch)",
+            "kernel_ms": kern_ms, "bytes_per_env_step": bpe,
+            "vm_words_written_per_env_step": words, "pms_written_per_env_step": pmw,
+            "issue": issue}
+
+
+def full_legs(args, env, dev, stream, dist, world, rank, seeds, reset_at, ff_total, K):
+    """--full: every leg beside the headline, on the headline's envs first
+    (external actions, fused rollout, replicas, parity), then on envs of their
+    own. Closes `env`. Returns the legs' entries of the result line."""
+    N = env.n_envs
+    P, V = CFG["pms"], CFG["vms"]
 
     # ---- external-action mode (the PPO path): vmp_step on i32[N, V] actions ----
     ext = _guard(bench_external, args, env, dev, stream, dist, world, P, V)
@@ -258,23 +366,9 @@ def main():
 
         if world == 1 and not args.no_cpu:
             # 48 envs per thread: ~1.5 s passes (16 per thread gave ~0.5 s
-            # passes and up to 6 % spread under the box's CPU quota)
+            # passes and up to 6 % spread under the host's CPU quota)
             cpu = cpu_baseline(CFG, args.cpu_threads, "same config", envs_per_thread=48)
 
-    bpe = step_bytes(P, V, words, pmw)
-    achieved = bpe * N / (kern_ms * 1e-3) / 1e9
-    traffic = None
-    issue = None
-    tpath = os.path.join(ROOT, "profiles", "traffic.json")
-    if os.path.exists(tpath):
-        try:
-            tj = json.load(open(tpath))
-            if tj.get("envs") == N and tj.get("bytes_per_launch"):
-                traffic = float(tj["bytes_per_launch"])
-            if tj.get("envs") == N and tj.get("SQ_INSTS_VALU"):
-                issue = issue_roofline(tj, N, kern_ms)
-        except Exception:
-            traffic = None
     env.close()
     period = None if args.period_steps <= 0 else _guard(bench_period, args, dev, rank, world,
                                                        dist, CFG)
@@ -287,24 +381,7 @@ def main():
         ppo_eval = _guard(bench_ppo_eval, args, dev, rank, world, dist)
     stress = None if args.no_ppo else _guard(bench_stress, args, dev, rank, world, dist)
     stress2k = None if args.no_ppo else _guard(bench_stress, args, dev, rank, world, dist, 2048)
-    out = {
-        "metric": METRIC, "value": value, "unit": "env-steps/s", "n_gpus": world, "steps": K,
-        "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / K, "higher_is_better": True,
-        "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-        "config": {"workload": "config/100.yml with vms=1000 (P100 V1000), FirstFit act + "
-                               "VmEnv.step fused, one launch per step", "envs_per_gpu": N,
-                   "global_envs": world * N, "pms": P, "vms": V,
-                   "arrival_rate": CFG["arrival_rate"], "service_length": CFG["service_length"],
-                   "reward_function": "wr", "policy": "firstfit", "mode": "train",
-                   "parallelism": f"env-shard x{world}", "steady_state_ff_steps": args.ff_steps,
-                   "phase_stagger": f"{args.phase_groups} groups x {args.phase_delta} steps: "
-                                    f"env ages {ff_total - (args.phase_groups - 1) * args.phase_delta}"
-                                    f"-{ff_total} at the window"},
-        "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
-                     "kernel": "vmp::k_env<16, true> (heuristic act+step, one step per launch)", "kernel_ms": kern_ms,
-                     "bytes_per_env_step": bpe, "vm_words_written_per_env_step": words,
-                     "pms_written_per_env_step": pmw, "issue": issue},
+    return {
         "cpu_baseline": cpu,
         "reference_cpu": _reference_cpu(),
         "fused_rollout": {"value": fused_value, "unit": "env-steps/s", "k_steps": kr},
@@ -319,10 +396,6 @@ def main():
         "stress_p1000_v10000": stress,
         "stress_p1000_v10000_2048envs": stress2k,
     }
-    if rank == 0:
-        print(json.dumps(out), flush=True)
-    if dist:
-        dist.destroy_process_group()
 
 
 N_SIMDS = 1024  # MI355X: 256 CUs x 4 SIMD-32

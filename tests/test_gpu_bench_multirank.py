@@ -1,7 +1,7 @@
 """bench.py's N > 1 path under test. The driver launches
 `python -m torch.distributed.run --nproc-per-node N bench.py --gpus N` on an
 8-GPU node at round end; here two gloo ranks share cuda:0
-(VMP_DIST_BACKEND=gloo, bench.py:111-117) and run every leg at reduced
+(VMP_DIST_BACKEND=gloo in bench.py's main) and run every leg (--full) at reduced
 sizes: NCCL-free init, barriers, max-over-ranks timing, the replica
 all-reduce / all-gather, the parity leg on rank 0, and the
 data-parallel PPO legs. The replica counters must equal ONE rank holding
@@ -19,7 +19,7 @@ pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 N_LOCAL = 1024
-SMALL = ["--steps", "5", "--warmup", "2", "--no-cpu", "--ff-steps", "300",
+SMALL = ["--full", "--steps", "5", "--warmup", "2", "--no-cpu", "--ff-steps", "300",
          "--phase-delta", "10", "--rollout-k", "20", "--ext-steps", "5"]
 
 

@@ -16,7 +16,7 @@ for v in $PARITY; do
 done
 for rep in $(seq 1 ${REPS:-2}); do
   for v in $VARIANTS; do
-    VMP_LIB_PATH=$VD/libvmp_$v.so timeout -k 10 300 python bench.py --steps 100 --warmup 10 --no-ppo \
+    VMP_LIB_PATH=$VD/libvmp_$v.so timeout -k 10 300 python bench.py --full --steps 100 --warmup 10 --no-ppo \
       --no-cpu $BENCH_ARGS > $O/b_${v}_$rep.log 2>&1
     rc=$?; [ $rc -ne 0 ] && { echo "bench $v rc=$rc"; tail -5 $O/b_${v}_$rep.log; exit $rc; }
     python - $O/b_${v}_$rep.log $v $rep <<'PY'

@@ -1,5 +1,6 @@
 #!/bin/bash
-# Full GPU check: the whole -m gpu suite, smoke(), then the default bench line.
+# Full GPU check: the whole -m gpu suite, smoke(), then the bench line with every leg.
+BENCH_ARGS="--full ${BENCH_ARGS:-}"
 cd "$GRAFT_REPO_ROOT" || exit 1
 mkdir -p gpurun_out
 timeout -k 10 900 python -u -m pytest tests -x -v -m gpu --timeout 300 --timeout-method thread > gpurun_out/gpu_tests.log 2>&1

@@ -1,5 +1,7 @@
 #!/bin/bash
-# k_env occupancy variants: the headline leg (no PPO / CPU legs) per library
+# k_env occupancy variants: the headline, external-action, fused-rollout and
+# parity legs (--full by VMP_BENCH_FULL; no PPO / CPU legs) per library
+export VMP_BENCH_FULL=1
 cd "$GRAFT_REPO_ROOT" || exit 1
 mkdir -p gpurun_out
 V=$PWD/vm-placement-migration-gym_amd/build/variants
