@@ -1,4 +1,4 @@
-"""Model check of the BF tie sort used by the env kernels (vmp_kernels.hip
+"""Model check of the BF tie sort used by the env kernels (csrc/vmp_np_sort.h
 wave_aquicksort / aquicksort_lds): numpy's scalar introsort (aquicksort_ +
 aheapsort_, npysort) restated serially, against the two transformations the
 kernels make — (1) only partitions intersecting the needed position range are

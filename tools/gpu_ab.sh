@@ -1,5 +1,5 @@
 #!/bin/bash
-# A/B of env-kernel library variants (tools/build_variant.sh NAME -D...):
+# A/B of env-kernel library variants (make -C vm-placement-migration-gym_amd variant NAME=x DEFS="-D..."):
 #   VARIANTS="base lh ..." [PARITY="lh ..."] [REPS=2] tools/gpu_ab.sh OUT
 # 1. for each variant in PARITY: tests/test_gpu_env.py through that library
 #    (every golden trajectory, the batched oracle replays, the headline steady

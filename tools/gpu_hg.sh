@@ -1,7 +1,7 @@
 #!/bin/bash
 # fused actor head: parity tests, then the head bench under measurement
 # overrides (HG_ENVS: space-separated VAR=value sets, "-" = none) and variant
-# builds (HG_VARIANTS, tools/build_variants.sh names) against the unfused path
+# builds (HG_VARIANTS, `make variant NAME=...` names) against the unfused path
 cd "$GRAFT_REPO_ROOT" || exit 1
 mkdir -p gpurun_out
 timeout -k 10 300 python -u -m pytest tests/test_gpu_actor_head.py -x -q --timeout 120 --timeout-method thread > gpurun_out/hg_tests.log 2>&1

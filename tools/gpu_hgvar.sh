@@ -1,5 +1,6 @@
 #!/bin/bash
-# bf16 head timing variants (tools/build_hg_variant.sh NAME -D...): the
+# bf16 head timing variants (make -C vm-placement-migration-gym_amd variant NAME=x DEFS="-D..."
+# VSRC=csrc/vmp_headgemm_bf16.hip): the
 # FWD_ONLY head bench through each library, REPS interleaved rounds.
 #   VARS="default hggo ..." [REPS=2] [PP=0] bash tools/gpu_hgvar.sh OUT
 # "default" = the normal vmp/libvmp.so; NAME@VAR=VALUE runs NAME with that

@@ -1,6 +1,6 @@
 #!/bin/bash
 # k_env issue-mix PMC passes (tools/prof_step.py) for the default library and
-# the variants in KV (tools/build_variants.sh names); per-kernel averages into
+# the variants in KV (`make variant NAME=...` names); per-kernel averages into
 # gpurun_out/kpmc/<lib>_<pass>.txt. LIST=1 also saves `rocprofv3 -L`.
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 mkdir -p gpurun_out/kpmc

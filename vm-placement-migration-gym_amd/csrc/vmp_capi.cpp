@@ -13,37 +13,9 @@
 #include <vector>
 
 #include "../../include/vmp.h"
+#include "vmp_kernels.h"
 #include "vmp_layout.h"
 #include "vmp_record.h"
-
-namespace vmp {
-constexpr int kStamps = 24;  // per-env phase clocks (diagnostic builds)
-template <int VPT, bool ONE>
-__global__ void k_env(EnvParams p, StepOut o);
-template <int VPT>
-__global__ void k_env_ext(EnvParams p, StepOut o);
-__global__ void k_rank(EnvParams p, int64_t *rank);
-__global__ void k_target_means_lds(EnvParams p);
-// k_env_big: one workgroup per env; its geometry (threads, slots per thread)
-// and launcher live with the kernel (vmp_kernels.hip)
-void big_geometry(int *nt, int *spt_max);
-void launch_big_env(int spt, bool one, int n_env, size_t lds, hipStream_t s, const EnvParams &p,
-                    const StepOut &o);
-int big_occupancy(int spt, size_t lds, int *static_lds);
-constexpr int kBigStaticLds = 4 * 1024;  // Tables + BigShared (static LDS of k_env_big)
-constexpr int kBigAccLds = 512;          // accepted sizes held in LDS
-__global__ void k_reset(EnvParams p, const int64_t *seeds, const uint8_t *env_mask, float *obs);
-__global__ void k_export(EnvParams p, int64_t *placement, double *vm_cpu, double *vm_mem,
-                         double *cpu, double *mem, int64_t *remaining, int64_t *rank);
-__global__ void k_counters(EnvParams p, int64_t *ctr, double *st);
-__global__ void k_target_means(EnvParams p);
-__global__ void k_record(EnvParams p, RecArgs r);
-__global__ void k_record_init(EnvParams p, RecArgs r);
-__global__ void k_record_close(EnvParams p, RecArgs r, uint32_t *hist, double *sums);
-__global__ void k_mask_bool(int64_t rows, int A, int W, const uint32_t *bits, uint8_t *mask);
-__global__ void k_act_obs(int P, int V, int policy, const float *obs, int32_t *act);
-int64_t quiet_violations_take();
-}  // namespace vmp
 
 using namespace vmp;
 
@@ -506,7 +478,7 @@ static int create_rest(vmp_handle *h, const vmp_config *cfg, int32_t n_env, cons
     int spt = 0, nt = 0;
     if (h->big) big_shape(h->V, spt, nt);
     const int64_t need = h->big ? per_env + kBigStaticLds + 4 * (int64_t)spt * nt
-                                : per_env * kEnvWavesPerBlock + 2048;
+                                : per_env * kEnvWavesPerBlock + kEnvStaticLds;
     if (need > 160 * 1024)
       return fail(VMP_EINVAL, "config too large for the LDS carve of this build");
   }

@@ -37,6 +37,7 @@
 #include <stdlib.h>
 
 #include "../../include/vmp.h"
+#include "vmp_head_dev.h"
 
 namespace vmp {
 
@@ -52,18 +53,9 @@ constexpr float kMasked = -1e7f;     // ppo.py:119
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
-__device__ __forceinline__ uint64_t mix64(uint64_t x) {  // splitmix64 finaliser
-  x += 0x9E3779B97F4A7C15ull;
-  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-  return x ^ (x >> 31);
-}
 // the same counter-based uniforms as vmp_policy.hip (coin flips agree with the
-// unfused head draw for draw)
-__device__ __forceinline__ float uniform_at(uint64_t seed, uint64_t ctr) {
-  const uint64_t h = mix64(seed ^ mix64(ctr));
-  return (float)(h >> 40) * (1.0f / 16777216.0f);
-}
+// unfused head draw for draw): vmp_head_dev.h's
+using hd::uniform_at;
 
 struct HGArgs {
   int B, K, V, A, W32, S, BN, n_tiles, mode, wait_index, stage_waves;
@@ -77,9 +69,7 @@ struct HGArgs {
   float *logits;  // nullable: raw logits [B][V*A] out
 };
 
-__device__ __forceinline__ uint64_t eff_seed(const HGArgs &a) {
-  return a.ctr ? a.seed ^ mix64(*a.ctr + 0x5851F42D4C957F2Dull) : a.seed;
-}
+__device__ __forceinline__ uint64_t eff_seed(const HGArgs &a) { return hd::eff_seed(a.seed, a.ctr); }
 
 // get_det_action: first max of the unmasked row (quad lanes c, c+4k)
 __device__ __forceinline__ void row_argmax(const HGArgs &a, const float *x, int64_t row, int c) {

@@ -37,6 +37,7 @@
 #include <stdlib.h>
 
 #include "../../include/vmp.h"
+#include "vmp_head_dev.h"
 
 #define LDSP __attribute__((address_space(3)))
 #define GLBP __attribute__((address_space(1)))
@@ -85,21 +86,10 @@ struct H16Args {
   int32_t *act_out;  // sampling: the drawn actions [B][V]
 };
 
-__device__ __forceinline__ uint64_t mix64(uint64_t x) {  // splitmix64 finaliser
-  x += 0x9E3779B97F4A7C15ull;
-  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-  return x ^ (x >> 31);
-}
 // the counter-based uniforms of vmp_policy.hip / vmp_headgemm.hip (stream
-// (seed, ctr), 24 random bits)
-__device__ __forceinline__ float uniform_at(uint64_t seed, uint64_t ctr) {
-  const uint64_t h = mix64(seed ^ mix64(ctr));
-  return (float)(h >> 40) * (1.0f / 16777216.0f);
-}
-__device__ __forceinline__ uint64_t eff_seed(const H16Args &a) {
-  return a.ctr ? a.seed ^ mix64(*a.ctr + 0x5851F42D4C957F2Dull) : a.seed;
-}
+// (seed, ctr), 24 random bits): vmp_head_dev.h's
+using hd::uniform_at;
+__device__ __forceinline__ uint64_t eff_seed(const H16Args &a) { return hd::eff_seed(a.seed, a.ctr); }
 
 __device__ __forceinline__ int lds_chunk(int row, int cl) { return cl ^ ((row >> 1) & 7); }
 

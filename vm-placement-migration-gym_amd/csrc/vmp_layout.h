@@ -1,5 +1,6 @@
 // vmp_layout.h — device-resident state layout and launch parameters shared by
-// the HIP kernels (vmp_kernels.hip) and the C-ABI host side (vmp_capi.cpp).
+// the HIP kernels (vmp_kernels.hip and its headers, vmp_record.hip) and the
+// C-ABI host side (vmp_capi.cpp).
 //
 // HBM layout, env-major so one wavefront streams one env's state with
 // coalesced 64-lane accesses (one wave per env):
@@ -34,10 +35,7 @@ namespace vmp {
 constexpr int kWaveSize = 64;
 constexpr int kWavesPerBlock = 4;
 // envs (waves) per workgroup of the env kernel k_env
-#ifndef VMP_ENV_WPB
-#define VMP_ENV_WPB 1
-#endif
-constexpr int kEnvWavesPerBlock = VMP_ENV_WPB;
+constexpr int kEnvWavesPerBlock = 1;
 constexpr int kMaxVPT = 16;  // VM slots per lane held in registers: V <= 1024
 constexpr int kMaxStepsPerLaunch = 256;  // rollout launches are split by the host
 constexpr int kSpecDraws = 64;           // speculative service draws per launch

@@ -24,17 +24,8 @@ namespace vmp {
 
 constexpr float kMaskedLogit = -1e7f;  // ppo.py:119 `logits[invalid_mask] = -1e7`
 
-__device__ __forceinline__ uint64_t mix64(uint64_t x) {  // splitmix64 finaliser
-  x += 0x9E3779B97F4A7C15ull;
-  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-  return x ^ (x >> 31);
-}
-// Counter-based uniform in [0, 1) with 24 random bits: stream (seed, ctr).
-__device__ __forceinline__ float uniform_at(uint64_t seed, uint64_t ctr) {
-  uint64_t h = mix64(seed ^ mix64(ctr));
-  return (float)(h >> 40) * (1.0f / 16777216.0f);
-}
+// the sampling stream (counter-based uniforms, launch seed) is vmp_head_dev.h's
+using hd::uniform_at;
 
 template <int G>
 __device__ __forceinline__ float gsum(float x) {
@@ -71,11 +62,7 @@ struct HeadArgs {
   float *row_lp, *row_ent;  // tiled kernels: per-row results [B*V]
 };
 
-// Seed of this launch: with a device counter (captured graphs replay the same
-// arguments) the counter's current value is mixed in.
-__device__ __forceinline__ uint64_t eff_seed(const HeadArgs &a) {
-  return a.ctr ? a.seed ^ mix64(*a.ctr + 0x5851F42D4C957F2Dull) : a.seed;
-}
+__device__ __forceinline__ uint64_t eff_seed(const HeadArgs &a) { return hd::eff_seed(a.seed, a.ctr); }
 
 // Loads one row into registers with the mask applied and, for SAMPLE/GIVEN,
 // the WAIT coin flip of PPOAgent.act (ppo.py:154-156):

@@ -1,6 +1,10 @@
-// vmp_record.h — recorder state shared by vmp_record.hip and vmp_capi.cpp.
+// vmp_record.h — recorder state and kernels shared by vmp_record.hip and
+// vmp_capi.cpp.
 #pragma once
+#include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include "vmp_layout.h"
 
 namespace vmp {
 struct RecArgs {
@@ -14,4 +18,7 @@ struct RecArgs {
   const uint8_t *valid;    // [N][V]
   const double *reward;    // [N]
 };
+__global__ void k_record(EnvParams p, RecArgs r);
+__global__ void k_record_init(EnvParams p, RecArgs r);
+__global__ void k_record_close(EnvParams p, RecArgs r, uint32_t *hist, double *sums);
 }  // namespace vmp
