@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define VMP_ABI_VERSION 11
+#define VMP_ABI_VERSION 12
 
 #define VMP_OK 0
 #define VMP_EINVAL (-1)
@@ -133,6 +133,25 @@ int vmp_set_eval(vmp_handle *h, int32_t eval_mode);
 int vmp_dims(const vmp_handle *h, int32_t *n_env, int32_t *P, int32_t *V, int32_t *A,
              int32_t *D);
 
+/* Per-env workload: env i draws arrivals ~ Poisson(arrival_rate[i]) (env.py:272) and planned
+ * runtimes ~ Poisson(service_length[i]) + 1 (env.py:289) from its next step on. HOST arrays of
+ * n_env doubles; either may be NULL = keep that quantity as it is. Values must be finite and
+ * >= 0 (VMP_EINVAL otherwise); on any failure the handle keeps its previous workload and stays
+ * usable. Env i then behaves bit for bit as a handle created with its pair in the config: the
+ * state, the RNG streams and the step hints are untouched, only the Poisson constants the
+ * step kernels read change (the three samplers, lam == 0 / < 10 / >= 10, may be mixed within
+ * one launch). Stream-ordered behind the launches already queued on the handle's stream; the
+ * call synchronises that stream before it returns, so it must not be made while the stream
+ * is capturing.
+ * Graphs: the first call moves the kernels' constants from the handle's single pair to a
+ * per-env array, so a graph captured BEFORE the first vmp_set_workload keeps reading the
+ * config's values and must be recaptured. Later calls rewrite that array in place: graphs
+ * captured after the first call stay valid across them and replay with the new values.
+ * (ABI 12) */
+int vmp_set_workload(vmp_handle *h, const double *arrival_rate, const double *service_length);
+/* Current per-env values (the config's for a handle never given a workload); HOST arrays, nullable. */
+int vmp_get_workload(const vmp_handle *h, double *arrival_rate, double *service_length);
+
 /* VmEnv.reset (env.py:180-226) for the envs whose env_mask byte is non-zero
  * (env_mask may be NULL = all). seeds: device int64[n_env] or NULL; a NULL
  * seeds array is reset(seed=None): streams continue and the VM-size
@@ -208,7 +227,12 @@ int vmp_get_rank(vmp_handle *h, int64_t *rank);
  * handle stood. Stream-ordered on the handle's stream (vmp_snapshot returns
  * after the copy; vmp_restore synchronises the stream once to check the
  * snapshot's descriptor). Not included: eval mode (vmp_set_eval) and the
- * Record recorder (re-enable it after a restore, as after a reset). */
+ * Record recorder (re-enable it after a restore, as after a reset).
+ * A handle given a per-env workload (vmp_set_workload) appends it to its
+ * snapshots (16 * n_env bytes more, counted by vmp_snapshot_bytes);
+ * vmp_restore then needs a handle whose current workload is bitwise the same,
+ * and refuses (VMP_EINVAL) a snapshot with a workload on a handle without one
+ * and the reverse. Handles never given one keep the earlier layout and size. */
 int vmp_snapshot_bytes(const vmp_handle *h, int64_t *bytes);
 int vmp_snapshot(vmp_handle *h, void *dst);
 int vmp_restore(vmp_handle *h, const void *src);

@@ -8,6 +8,7 @@
 
 #include <cmath>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -118,11 +119,21 @@ struct vmp_handle {
   int32_t *rec_act;   // scratch action / validity / reward when the caller passes none
   uint8_t *rec_valid;
   double *rec_reward;
+  // per-env workload (vmp_set_workload); all null / 0 for a handle never given one
+  double *wl;           // host f64 [N][2]: arrival_rate, service_length of every env
+  PoisConst *wl_rec;    // host mirror of pois_env
+  PoisConst *pois_env;  // device [N][2], prm.pois once set (address stable from then on);
+                        // non-null selects the WL = true kernels (launch_env)
+  double *lg_shared;    // device loggam table shared by all PTRS records of pois_env
+  int32_t lg_shared_n;
 };
 
 namespace {
 
-int setup_pois(double lam, PoisConst &c, double **dev_tab, std::vector<double> &host_tab) {
+// The constants of Poisson(lam) and the length tab_n of the loggam table its
+// PTRS draws index (entry k = loggam(k), the same for every lam); loggam_tab
+// is left null for the caller to point at a table of at least tab_n entries.
+void pois_consts(double lam, PoisConst &c) {
   std::memset(&c, 0, sizeof(c));
   c.lam = lam;
   if (lam == 0) {
@@ -141,11 +152,29 @@ int setup_pois(double lam, PoisConst &c, double **dev_tab, std::vector<double> &
     c.log_invalpha = std::log(c.invalpha);
     int64_t n = (int64_t)(lam + 16.0 * slam + 64.0);
     if (n > (1 << 22)) n = 1 << 22;
-    host_tab.resize((size_t)n);
-    for (int64_t k = 0; k < n; k++) host_tab[(size_t)k] = loggam_host((double)k);
     c.tab_n = (int32_t)n;
-    HIP_TRY(dev_malloc(dev_tab, sizeof(double) * n));
-    HIP_TRY(hipMemcpy(*dev_tab, host_tab.data(), sizeof(double) * n, hipMemcpyHostToDevice));
+  }
+}
+
+// A device table loggam(k), k in [0, n).
+int make_loggam_tab(int64_t n, double **dev_tab) {
+  std::vector<double> host_tab((size_t)n);
+  for (int64_t k = 0; k < n; k++) host_tab[(size_t)k] = loggam_host((double)k);
+  HIP_TRY(dev_malloc(dev_tab, sizeof(double) * n));
+  const hipError_t e = hipMemcpy(*dev_tab, host_tab.data(), sizeof(double) * n, hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    dev_free(*dev_tab);
+    *dev_tab = nullptr;
+    return fail(VMP_EDEVICE, std::string("loggam table copy: ") + hipGetErrorString(e));
+  }
+  return VMP_OK;
+}
+
+int setup_pois(double lam, PoisConst &c, double **dev_tab) {
+  pois_consts(lam, c);
+  if (c.kind == 2) {
+    const int rc = make_loggam_tab(c.tab_n, dev_tab);
+    if (rc != VMP_OK) return rc;
     c.loggam_tab = *dev_tab;
   }
   return VMP_OK;
@@ -279,23 +308,25 @@ void carve_big(vmp_handle *h) {
   p.lds_wave_bytes = (int32_t)off;
 }
 
+// WL: the handle has a per-env workload (the kernels of vmp_kernels_wl.hip)
+template <bool WL>
 void launch_ext(int need, dim3 grid, dim3 block, size_t lds, hipStream_t s, const EnvParams &p,
                 const StepOut &o) {
-  if (need <= 1) hipLaunchKernelGGL((k_env_ext<1>), grid, block, lds, s, p, o);
-  else if (need <= 2) hipLaunchKernelGGL((k_env_ext<2>), grid, block, lds, s, p, o);
-  else if (need <= 4) hipLaunchKernelGGL((k_env_ext<4>), grid, block, lds, s, p, o);
-  else if (need <= 8) hipLaunchKernelGGL((k_env_ext<8>), grid, block, lds, s, p, o);
-  else hipLaunchKernelGGL((k_env_ext<16>), grid, block, lds, s, p, o);
+  if (need <= 1) hipLaunchKernelGGL((k_env_ext<1, WL>), grid, block, lds, s, p, o);
+  else if (need <= 2) hipLaunchKernelGGL((k_env_ext<2, WL>), grid, block, lds, s, p, o);
+  else if (need <= 4) hipLaunchKernelGGL((k_env_ext<4, WL>), grid, block, lds, s, p, o);
+  else if (need <= 8) hipLaunchKernelGGL((k_env_ext<8, WL>), grid, block, lds, s, p, o);
+  else hipLaunchKernelGGL((k_env_ext<16, WL>), grid, block, lds, s, p, o);
 }
 
-template <bool ONE>
+template <bool ONE, bool WL>
 void launch_vpt(int need, dim3 grid, dim3 block, size_t lds, hipStream_t s, const EnvParams &p,
                 const StepOut &o) {
-  if (need <= 1) hipLaunchKernelGGL((k_env<1, ONE>), grid, block, lds, s, p, o);
-  else if (need <= 2) hipLaunchKernelGGL((k_env<2, ONE>), grid, block, lds, s, p, o);
-  else if (need <= 4) hipLaunchKernelGGL((k_env<4, ONE>), grid, block, lds, s, p, o);
-  else if (need <= 8) hipLaunchKernelGGL((k_env<8, ONE>), grid, block, lds, s, p, o);
-  else hipLaunchKernelGGL((k_env<16, ONE>), grid, block, lds, s, p, o);
+  if (need <= 1) hipLaunchKernelGGL((k_env<1, ONE, WL>), grid, block, lds, s, p, o);
+  else if (need <= 2) hipLaunchKernelGGL((k_env<2, ONE, WL>), grid, block, lds, s, p, o);
+  else if (need <= 4) hipLaunchKernelGGL((k_env<4, ONE, WL>), grid, block, lds, s, p, o);
+  else if (need <= 8) hipLaunchKernelGGL((k_env<8, ONE, WL>), grid, block, lds, s, p, o);
+  else hipLaunchKernelGGL((k_env<16, ONE, WL>), grid, block, lds, s, p, o);
 }
 
 // k_env_big's shape: the fewest slots per thread that fit 384 threads, and the
@@ -309,6 +340,7 @@ void big_shape(int64_t V, int &spt, int &nt) {
 int launch_env(vmp_handle *h, const StepOut &o) {
   dim3 grid((h->N + kEnvWavesPerBlock - 1) / kEnvWavesPerBlock), block(64 * kEnvWavesPerBlock);
   EnvParams p = h->prm;
+  const bool wl = h->pois_env != nullptr;  // p.pois is [N][2]: the WL kernels
   // per-launch region: speculative service draws (state + value) and arrivals
   p.scap = kSpecDraws;
   const int64_t pre = 20 * (int64_t)p.scap + 4 * (int64_t)(o.k_steps > 0 ? o.k_steps : 1);
@@ -320,16 +352,23 @@ int launch_env(vmp_handle *h, const StepOut &o) {
     int spt, nt;
     big_shape(h->V, spt, nt);
     const size_t lds1 = (size_t)p.lds_wave_bytes + 4 * (size_t)spt * nt;
-    launch_big_env(spt, o.k_steps == 1, h->N, lds1, h->stream, p, o);
+    if (wl) launch_big_env_wl(spt, o.k_steps == 1, h->N, lds1, h->stream, p, o);
+    else launch_big_env(spt, o.k_steps == 1, h->N, lds1, h->stream, p, o);
     HIP_TRY(hipGetLastError());
     return VMP_OK;
   }
   const int need = (h->V + 63) / 64;
   if (o.actions) {  // external actions: vmp_step, one step
     if (o.k_steps != 1) return fail(VMP_EINVAL, "external actions take one step per launch");
-    launch_ext(need, grid, block, lds, h->stream, p, o);
-  } else if (o.k_steps == 1) launch_vpt<true>(need, grid, block, lds, h->stream, p, o);
-  else launch_vpt<false>(need, grid, block, lds, h->stream, p, o);
+    if (wl) launch_ext<true>(need, grid, block, lds, h->stream, p, o);
+    else launch_ext<false>(need, grid, block, lds, h->stream, p, o);
+  } else if (o.k_steps == 1) {
+    if (wl) launch_vpt<true, true>(need, grid, block, lds, h->stream, p, o);
+    else launch_vpt<true, false>(need, grid, block, lds, h->stream, p, o);
+  } else {
+    if (wl) launch_vpt<false, true>(need, grid, block, lds, h->stream, p, o);
+    else launch_vpt<false, false>(need, grid, block, lds, h->stream, p, o);
+  }
   HIP_TRY(hipGetLastError());
   return VMP_OK;
 }
@@ -386,9 +425,8 @@ int vmp_create(const vmp_config *cfg, int32_t n_env, const int64_t *seeds, int32
   }
   h->device = device;
   h->stream = nullptr;
-  std::vector<double> t1, t2;
-  int rc = setup_pois(cfg->arrival_rate, h->arr, &h->lg_arr, t1);
-  if (rc == VMP_OK) rc = setup_pois(cfg->service_length, h->svc, &h->lg_svc, t2);
+  int rc = setup_pois(cfg->arrival_rate, h->arr, &h->lg_arr);
+  if (rc == VMP_OK) rc = setup_pois(cfg->service_length, h->svc, &h->lg_svc);
   if (rc != VMP_OK) {
     const std::string msg = g_err;
     vmp_destroy(h);  // frees whatever the first setup_pois allocated
@@ -509,8 +547,117 @@ int vmp_destroy(vmp_handle *h) {
   dev_free(h->jump_dev);
   dev_free(h->bigscr);
   dev_free(h->stamps);
+  dev_free(h->pois_env);
+  dev_free(h->lg_shared);
+  std::free(h->wl);
+  std::free(h->wl_rec);
   vmp_record_enable(h, 0);
   delete h;
+  return VMP_OK;
+}
+
+// ---- per-env workload ----
+// Env i's pair of records is what vmp_create computes for a config of its
+// (arrival_rate, service_length), except that every PTRS record points into
+// one loggam table (entry k = loggam(k) whatever the rate) sized for the
+// largest tab_n in use; each record keeps its own tab_n, so an env takes the
+// table / loggam_far branch exactly where a homogeneous handle of its rate does.
+int vmp_set_workload(vmp_handle *h, const double *arrival_rate, const double *service_length) {
+  if (!h) return fail(VMP_EINVAL, "null handle");
+  if (!arrival_rate && !service_length) return VMP_OK;
+  const size_t N = (size_t)h->N;
+  for (size_t i = 0; i < N; i++) {
+    const double a = arrival_rate ? arrival_rate[i] : 0.0, s = service_length ? service_length[i] : 0.0;
+    if (!std::isfinite(a) || !std::isfinite(s) || a < 0 || s < 0)
+      return fail(VMP_EINVAL, "arrival_rate and service_length must be finite and >= 0");
+  }
+  std::vector<double> wl(2 * N);
+  std::vector<PoisConst> rec(2 * N);
+  int32_t need_n = 0;
+  for (size_t i = 0; i < N; i++) {
+    wl[2 * i] = arrival_rate ? arrival_rate[i] : h->wl ? h->wl[2 * i] : h->cfg.arrival_rate;
+    wl[2 * i + 1] = service_length ? service_length[i] : h->wl ? h->wl[2 * i + 1] : h->cfg.service_length;
+    for (int j = 0; j < 2; j++) {
+      pois_consts(wl[2 * i + j], rec[2 * i + j]);
+      if (rec[2 * i + j].tab_n > need_n) need_n = rec[2 * i + j].tab_n;
+    }
+  }
+  // host copies first: nothing below them can fail halfway
+  const bool first = h->pois_env == nullptr;
+  double *wl_new = h->wl;
+  PoisConst *rec_new = h->wl_rec;
+  if (first) {
+    wl_new = (double *)std::malloc(sizeof(double) * 2 * N);
+    rec_new = (PoisConst *)std::malloc(sizeof(PoisConst) * 2 * N);
+    if (!wl_new || !rec_new) {
+      std::free(wl_new);
+      std::free(rec_new);
+      return fail(VMP_EOOM, "vmp_set_workload: host allocation failed");
+    }
+  }
+  double *tab = h->lg_shared, *tab_new = nullptr;
+  PoisConst *dev_new = nullptr;
+  int rc = VMP_OK;
+  if (need_n > h->lg_shared_n) {
+    rc = make_loggam_tab(need_n, &tab_new);
+    tab = tab_new;
+  }
+  if (rc == VMP_OK && first) {
+    const hipError_t e = dev_malloc(&dev_new, sizeof(PoisConst) * 2 * N);
+    if (e != hipSuccess)
+      rc = fail(e == hipErrorOutOfMemory ? VMP_EOOM : VMP_EDEVICE,
+                std::string("vmp_set_workload: ") + hipGetErrorString(e));
+  }
+  if (rc == VMP_OK) {
+    for (PoisConst &c : rec)
+      if (c.kind == 2) c.loggam_tab = tab;
+    // stream-ordered behind the launches already queued, which read the old
+    // values; the call returns once the new ones are in place
+    PoisConst *dst = first ? dev_new : h->pois_env;
+    hipError_t e = hipMemcpyAsync(dst, rec.data(), sizeof(PoisConst) * 2 * N, hipMemcpyHostToDevice,
+                                  h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) {
+      rc = fail(VMP_EDEVICE, std::string("vmp_set_workload copy: ") + hipGetErrorString(e));
+      if (!first) {  // put the previous records back before the new table goes
+        (void)hipMemcpyAsync(dst, h->wl_rec, sizeof(PoisConst) * 2 * N, hipMemcpyHostToDevice, h->stream);
+        (void)hipStreamSynchronize(h->stream);
+      }
+    }
+  }
+  if (rc != VMP_OK) {
+    const std::string msg = g_err;
+    dev_free(tab_new);
+    dev_free(dev_new);
+    if (first) {
+      std::free(wl_new);
+      std::free(rec_new);
+    }
+    return fail(rc, msg);
+  }
+  // commit. No queued launch reads the old table any more (synchronised above)
+  if (tab_new) {
+    dev_free(h->lg_shared);
+    h->lg_shared = tab_new;
+    h->lg_shared_n = need_n;
+  }
+  std::memcpy(wl_new, wl.data(), sizeof(double) * 2 * N);
+  std::memcpy(rec_new, rec.data(), sizeof(PoisConst) * 2 * N);
+  h->wl = wl_new;
+  h->wl_rec = rec_new;
+  if (first) {
+    h->pois_env = dev_new;
+    h->prm.pois = dev_new;  // launch_env picks the WL kernels from now on
+  }
+  return VMP_OK;
+}
+
+int vmp_get_workload(const vmp_handle *h, double *arrival_rate, double *service_length) {
+  if (!h) return fail(VMP_EINVAL, "null handle");
+  for (int32_t i = 0; i < h->N; i++) {
+    if (arrival_rate) arrival_rate[i] = h->wl ? h->wl[2 * i] : h->cfg.arrival_rate;
+    if (service_length) service_length[i] = h->wl ? h->wl[2 * i + 1] : h->cfg.service_length;
+  }
   return VMP_OK;
 }
 
@@ -820,11 +967,12 @@ struct SnapDesc {
   int32_t abi, hdr_bytes;
   int32_t N, P, V, A;
   vmp_config cfg;  // seed excluded from the compatibility check
+  int32_t workload;  // 1: the handle had a per-env workload, f64 [N][2] follows the VM words
 };
 static_assert(sizeof(SnapDesc) <= kSnapHead, "snapshot descriptor exceeds its header");
 int64_t snap_bytes(const vmp_handle *h) {
   return kSnapHead + (int64_t)sizeof(EnvHdr) * h->N + 16 * (int64_t)h->N * h->P +
-         4 * (int64_t)h->N * vm_pitch(h->V);
+         4 * (int64_t)h->N * vm_pitch(h->V) + (h->wl ? 16 * (int64_t)h->N : 0);
 }
 bool same_config(const vmp_config &a, const vmp_config &b) {
   vmp_config x = a, y = b;
@@ -851,14 +999,18 @@ int vmp_snapshot(vmp_handle *h, void *dst) {
   d.hdr_bytes = (int32_t)sizeof(EnvHdr);
   d.N = h->N, d.P = h->P, d.V = h->V, d.A = h->A;
   d.cfg = h->cfg;
+  d.workload = h->wl ? 1 : 0;
   std::memcpy(head, &d, sizeof(d));
   uint8_t *o = (uint8_t *)dst;
   const size_t nh = sizeof(EnvHdr) * (size_t)h->N, np = 16 * (size_t)h->N * h->P;
   HIP_TRY(hipMemcpyAsync(o, head, kSnapHead, hipMemcpyHostToDevice, h->stream));
   HIP_TRY(hipMemcpyAsync(o + kSnapHead, h->hdr, nh, hipMemcpyDeviceToDevice, h->stream));
   HIP_TRY(hipMemcpyAsync(o + kSnapHead + nh, h->pm, np, hipMemcpyDeviceToDevice, h->stream));
-  HIP_TRY(hipMemcpyAsync(o + kSnapHead + nh + np, h->vmw, 4 * (size_t)h->N * vm_pitch(h->V),
-                         hipMemcpyDeviceToDevice, h->stream));
+  const size_t nv = 4 * (size_t)h->N * vm_pitch(h->V);
+  HIP_TRY(hipMemcpyAsync(o + kSnapHead + nh + np, h->vmw, nv, hipMemcpyDeviceToDevice, h->stream));
+  if (h->wl)
+    HIP_TRY(hipMemcpyAsync(o + kSnapHead + nh + np + nv, h->wl, 16 * (size_t)h->N,
+                           hipMemcpyHostToDevice, h->stream));
   // the descriptor's host copy is a stack buffer: the call returns after it is read
   HIP_TRY(hipStreamSynchronize(h->stream));
   return VMP_OK;
@@ -876,6 +1028,16 @@ int vmp_restore(vmp_handle *h, const void *src) {
     return fail(VMP_EINVAL, "vmp_restore: snapshot of another env count or config");
   const uint8_t *s = (const uint8_t *)src;
   const size_t nh = sizeof(EnvHdr) * (size_t)h->N, np = 16 * (size_t)h->N * h->P;
+  // the env state continues bit-exactly only under the workload it ran with
+  if ((d.workload != 0) != (h->wl != nullptr))
+    return fail(VMP_EINVAL, "vmp_restore: snapshot and handle differ in having a per-env workload");
+  if (h->wl) {
+    std::vector<double> w(2 * (size_t)h->N);
+    HIP_TRY(hipMemcpy(w.data(), s + kSnapHead + nh + np + 4 * (size_t)h->N * vm_pitch(h->V),
+                      16 * (size_t)h->N, hipMemcpyDeviceToHost));
+    if (std::memcmp(w.data(), h->wl, 16 * (size_t)h->N) != 0)
+      return fail(VMP_EINVAL, "vmp_restore: snapshot of another per-env workload");
+  }
   HIP_TRY(hipMemcpyAsync(h->hdr, s + kSnapHead, nh, hipMemcpyDeviceToDevice, h->stream));
   HIP_TRY(hipMemcpyAsync(h->pm, s + kSnapHead + nh, np, hipMemcpyDeviceToDevice, h->stream));
   HIP_TRY(hipMemcpyAsync(h->vmw, s + kSnapHead + nh + np, 4 * (size_t)h->N * vm_pitch(h->V),

@@ -859,7 +859,7 @@ __device__ __forceinline__ void big_store_obs(const EnvParams &p, const Lds &L, 
 // each step and written back as they change (placed, suspended, finished,
 // accepted), so no per-slot time registers live across the step; the low
 // halves live in LDS (W) and are stored by big_store (`dirty`).
-template <int SPT>
+template <int SPT, bool WL>
 __device__ __forceinline__ double big_tail(const EnvParams &p, const Lds &L, const Tables &T,
                                            BigShared &B, uint32_t LDSP *W, SMask run0,
                                            SMask &dirty, int kstep, bool &terminated,
@@ -982,7 +982,7 @@ VMP_SLOOP
         for (int64_t j = j0; j < j1; j++) {
           const int cc = (int)rint((p.seq_lo + p.seq_range * next_double(r1)) * 100.0);
           const int cm = (int)rint((p.seq_lo + p.seq_range * next_double(r2)) * 100.0);
-          const uint32_t rr = svc_take(p, L);
+          const uint32_t rr = svc_take<WL>(p, L, e);
           if (lane == 0) {
             if (acc_g) {
               gsc[j] = (uint8_t)cc;
@@ -1099,7 +1099,8 @@ VMP_SLOOP
 // step's registers (rem[] above all) are dead after the state store instead of
 // live around the K-step loop's back edge, which spilled them around the sums.
 // (both instantiations are register-allocated for 2 waves per SIMD)
-template <int SPT, bool ONE>
+// WL = true: the kernel of handles with a per-env workload (env_pois).
+template <int SPT, bool ONE, bool WL = false>
 __global__ __launch_bounds__(kBigNT, 2) void k_env_big(EnvParams p, StepOut o) {
   extern __shared__ __align__(16) char lds[];
   __shared__ Tables T;
@@ -1123,7 +1124,7 @@ __global__ __launch_bounds__(kBigNT, 2) void k_env_big(EnvParams p, StepOut o) {
     T.fcent[i] = (float)((double)i / 100.0);
   }
   constexpr int kPoisWords = (int)(2 * sizeof(PoisConst) / 4);
-  if (t < kPoisWords) reinterpret_cast<uint32_t *>(T.pois)[t] = gptr(reinterpret_cast<const uint32_t *>(p.pois))[t];
+  if (t < kPoisWords) reinterpret_cast<uint32_t *>(T.pois)[t] = gptr(reinterpret_cast<const uint32_t *>(env_pois<WL>(p, e)))[t];
   // every global load of the env's state is issued before the first LDS store
   // (indices clamped, not branched on, so the loads are unconditional):
   // header, the first 4*NT PM words, the VM words
@@ -1190,7 +1191,7 @@ VMP_SLOOP
       L.hdr->suspend_action += n_susp;
     }
     __syncthreads();
-    const double r = big_tail<SPT>(p, L, T, B, W, run0, dirty, k, term,
+    const double r = big_tail<SPT, WL>(p, L, T, B, W, run0, dirty, k, term,
                                    last && o.obs ? o.obs + (int64_t)e * p.D : nullptr, last,
                                    o.policy >= 0, e
                                    STAMP_ARGS);
@@ -1258,6 +1259,18 @@ VMP_SLOOP
     o[7] = (uint32_t)__builtin_amdgcn_s_getreg((31 << 11) | 20);  // XCC_ID
   }
 #endif
+}
+
+// host side: launch the instantiation for `spt` slots per thread
+template <bool ONE, bool WL>
+static void launch_big_one(int spt, int n_env, size_t lds, hipStream_t s, const EnvParams &p,
+                           const StepOut &o) {
+  const dim3 grid(n_env), block(kBigNT);
+  if (spt == 4) hipLaunchKernelGGL((k_env_big<4, ONE, WL>), grid, block, lds, s, p, o);
+  else if (spt == 8) hipLaunchKernelGGL((k_env_big<8, ONE, WL>), grid, block, lds, s, p, o);
+  else if (spt == 16) hipLaunchKernelGGL((k_env_big<16, ONE, WL>), grid, block, lds, s, p, o);
+  else
+  hipLaunchKernelGGL((k_env_big<kBigMaxSPT, ONE, WL>), grid, block, lds, s, p, o);
 }
 
 }  // namespace vmp

@@ -491,14 +491,24 @@ __device__ __forceinline__ void predraw(const EnvParams &p, const Lds &L, const 
   wsync();
 }
 
-// Next planned runtime (rng4.poisson(L) + 1, env.py:289) for an accepted VM.
-__device__ __forceinline__ uint32_t svc_take(const EnvParams &p, const Lds &L) {
+// The Poisson records of env e: the handle's one pair, or (WL, the kernels of
+// handles with a per-env workload) the env's own pair of p.pois[N][2]. e is
+// wave-uniform, so this is scalar address arithmetic.
+template <bool WL>
+__device__ __forceinline__ const PoisConst *env_pois(const EnvParams &p, int e) {
+  return WL ? p.pois + 2 * (int64_t)e : p.pois;
+}
+
+// Next planned runtime (rng4.poisson(L) + 1, env.py:289) for an accepted VM
+// of env e (the fallback reads that env's service-length record).
+template <bool WL>
+__device__ __forceinline__ uint32_t svc_take(const EnvParams &p, const Lds &L, int e) {
   const int S = L.svcinfo[0], used = L.svcinfo[1];
   uint32_t x;
   if (used < S) {
     x = L.svc[used];
   } else {
-    x = svc_fallback(L.svcfb, &L.hdr->rng[3][2], p.pois + 1);
+    x = svc_fallback(L.svcfb, &L.hdr->rng[3][2], env_pois<WL>(p, e) + 1);
   }
   wsync();
   if (lane_id() == 0) L.svcinfo[1] = used + 1;

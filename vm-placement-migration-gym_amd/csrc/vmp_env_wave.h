@@ -262,13 +262,13 @@ __device__ __forceinline__ void external_apply(const EnvParams &p, const Lds &L,
 // waiting: remaining <= 1, i.e. placed now it finishes now), accepted words are
 // stored at once through `vmo`, and the caller fixes the finish keys of placed /
 // suspended VMs in memory; rem[] is then unused.
-template <int VPT, bool LAZY>
+template <int VPT, bool LAZY, bool WL>
 __device__ __forceinline__ double env_tail(const EnvParams &p, const Lds &L, const Tables &T,
                                            uint32_t (&wa)[VPT], uint32_t (&rem)[VPT],
                                            uint32_t run0, uint32_t fb, uint32_t &dirty,
                                            uint32_t *vmo, int kstep, bool ext,
                                            bool quiet_in, bool &terminated, bool &calm,
-                                           bool &has_ex STAMP_PARAMS) {
+                                           bool &has_ex, int e STAMP_PARAMS) {
   const int lane = lane_id();
   const int P = p.P, WAIT = p.P, NUL = p.P + 1;
   EnvHdr LDSP *H = L.hdr;
@@ -352,7 +352,7 @@ __device__ __forceinline__ double env_tail(const EnvParams &p, const Lds &L, con
     for (int j = 0; j < k; j++) {
       const int cc = (int)rint((p.seq_lo + p.seq_range * next_double(r1)) * 100.0);
       const int cm = (int)rint((p.seq_lo + p.seq_range * next_double(r2)) * 100.0);
-      const uint32_t rr = svc_take(p, L);
+      const uint32_t rr = svc_take<WL>(p, L, e);
       const int v = L.nulls[j];
       if (lane == (v & 63)) {
 #pragma unroll
@@ -566,7 +566,9 @@ __device__ __forceinline__ void write_mask(const EnvParams &p, const Lds &L, con
 // is a separate instantiation so profiles tell it apart from fused rollouts.
 // EXT = true: the external-action step (vmp_step), its own kernel k_env_ext so
 // the heuristic's registers do not weigh on it and vice versa.
-template <int VPT, bool ONE, bool EXT>
+// WL = true: the handle has a per-env workload (vmp_set_workload); the only
+// difference is where the env's Poisson constants are read from (env_pois).
+template <int VPT, bool ONE, bool EXT, bool WL>
 __device__ __forceinline__ void env_body(const EnvParams &p, const StepOut &o) {
   extern __shared__ __align__(16) char lds[];
   __shared__ Tables T;
@@ -592,9 +594,12 @@ __device__ __forceinline__ void env_body(const EnvParams &p, const StepOut &o) {
   __builtin_amdgcn_s_setprio(2);
   const uint64_t hv = gptr(reinterpret_cast<const uint64_t *>(p.hdr + e))[lane & 31];
   // Poisson constants for the block's LDS copy (issued before the state loads,
-  // so waiting for them never waits on the state)
+  // so waiting for them never waits on the state): the env's own pair, one
+  // env per workgroup (e is wave-uniform: scalar address arithmetic)
+  static_assert(kEnvWavesPerBlock == 1, "Tables::pois holds one env's Poisson constants");
   constexpr int kPoisWords = (int)(2 * sizeof(PoisConst) / 4);
-  const uint32_t pw = gptr(reinterpret_cast<const uint32_t *>(p.pois))[threadIdx.x % kPoisWords];
+  const uint32_t pw =
+      gptr(reinterpret_cast<const uint32_t *>(env_pois<WL>(p, e)))[threadIdx.x % kPoisWords];
   // this lane's PCG64 jump entry (lane-parallel draws), right behind the header
   U128 JA{0, 0}, JM{0, 0};
   if (o.k_steps > 0) {
@@ -774,8 +779,8 @@ __device__ __forceinline__ void env_body(const EnvParams &p, const StepOut &o) {
     }
     wsync();
     bool calm = false;
-    const double r = env_tail<VPT, ONE>(p, L, T, wa, rem, run0, fb, dirty, vmo, k, EXT, quiet,
-                                        term, calm, has_ex STAMP_ARGS);
+    const double r = env_tail<VPT, ONE, WL>(p, L, T, wa, rem, run0, fb, dirty, vmo, k, EXT, quiet,
+                                        term, calm, has_ex, e STAMP_ARGS);
     // the next step's skip: nothing fit (1), or every placement was rejected
     // (2); a skipped step passes its kind on while nothing changes
     qkind = (EXT || !calm) ? 0 : quiet ? qkind : (!fit_any ? 1 : (n_place == 0 ? 2 : 0));
@@ -858,33 +863,39 @@ __device__ __forceinline__ void env_body(const EnvParams &p, const StepOut &o) {
   STAMP_FLUSH();
 }
 
-template <int VPT, bool ONE>
+template <int VPT, bool ONE, bool WL>
 __global__ __launch_bounds__(64 * kEnvWavesPerBlock, ONE ? VMP_WAVES_PER_EU_ONE : VMP_WAVES_PER_EU) void k_env(EnvParams p, StepOut o) {
-  env_body<VPT, ONE, false>(p, o);
+  env_body<VPT, ONE, false, WL>(p, o);
 }
 // VPT 1 (V <= 64, the PPO eval's config/10.yml): 4 waves per SIMD, so a
 // 4 096-env step is one round of waves on the 256 CUs (at 3, 131 VGPRs, a
 // third of the envs ran in a second round)
-template <int VPT>
+template <int VPT, bool WL>
 __global__ __launch_bounds__(64 * kEnvWavesPerBlock, VPT == 1 ? 4 : VMP_WAVES_PER_EU_ONE) void k_env_ext(EnvParams p, StepOut o) {
-  env_body<VPT, true, true>(p, o);
+  env_body<VPT, true, true, WL>(p, o);
 }
 
-template __global__ void k_env_ext<1>(EnvParams, StepOut);
-template __global__ void k_env_ext<2>(EnvParams, StepOut);
-template __global__ void k_env_ext<4>(EnvParams, StepOut);
-template __global__ void k_env_ext<8>(EnvParams, StepOut);
-template __global__ void k_env_ext<16>(EnvParams, StepOut);
-template __global__ void k_env<1, false>(EnvParams, StepOut);
-template __global__ void k_env<1, true>(EnvParams, StepOut);
-template __global__ void k_env<2, false>(EnvParams, StepOut);
-template __global__ void k_env<2, true>(EnvParams, StepOut);
-template __global__ void k_env<4, false>(EnvParams, StepOut);
-template __global__ void k_env<4, true>(EnvParams, StepOut);
-template __global__ void k_env<8, false>(EnvParams, StepOut);
-template __global__ void k_env<8, true>(EnvParams, StepOut);
-template __global__ void k_env<16, false>(EnvParams, StepOut);
-template __global__ void k_env<16, true>(EnvParams, StepOut);
+// One translation unit instantiates one workload variant: vmp_kernels.hip the
+// kernels of handles with the config's one workload, vmp_kernels_wl.hip
+// (VMP_ENV_WL = true) those of handles with a per-env workload.
+#ifndef VMP_ENV_WL
+#define VMP_ENV_WL false
+#endif
+template __global__ void k_env_ext<1, VMP_ENV_WL>(EnvParams, StepOut);
+template __global__ void k_env_ext<2, VMP_ENV_WL>(EnvParams, StepOut);
+template __global__ void k_env_ext<4, VMP_ENV_WL>(EnvParams, StepOut);
+template __global__ void k_env_ext<8, VMP_ENV_WL>(EnvParams, StepOut);
+template __global__ void k_env_ext<16, VMP_ENV_WL>(EnvParams, StepOut);
+template __global__ void k_env<1, false, VMP_ENV_WL>(EnvParams, StepOut);
+template __global__ void k_env<1, true, VMP_ENV_WL>(EnvParams, StepOut);
+template __global__ void k_env<2, false, VMP_ENV_WL>(EnvParams, StepOut);
+template __global__ void k_env<2, true, VMP_ENV_WL>(EnvParams, StepOut);
+template __global__ void k_env<4, false, VMP_ENV_WL>(EnvParams, StepOut);
+template __global__ void k_env<4, true, VMP_ENV_WL>(EnvParams, StepOut);
+template __global__ void k_env<8, false, VMP_ENV_WL>(EnvParams, StepOut);
+template __global__ void k_env<8, true, VMP_ENV_WL>(EnvParams, StepOut);
+template __global__ void k_env<16, false, VMP_ENV_WL>(EnvParams, StepOut);
+template __global__ void k_env<16, true, VMP_ENV_WL>(EnvParams, StepOut);
 
 }  // namespace vmp
 

@@ -23,9 +23,12 @@ constexpr int kEnvStaticLds = 2048;  // k_env / k_env_ext: allowance for Tables
 constexpr int kBigStaticLds = 4720;  // k_env_big: Tables + BigShared, exactly
 constexpr int kBigAccLds = 512;      // k_env_big: accepted sizes held in LDS
 
-template <int VPT, bool ONE>
+// WL = true: the instantiations for handles with a per-env workload
+// (vmp_set_workload), in a translation unit of their own (vmp_kernels_wl.hip);
+// handles without one run the WL = false kernels, whose code does not change
+template <int VPT, bool ONE, bool WL = false>
 __global__ void k_env(EnvParams p, StepOut o);
-template <int VPT>
+template <int VPT, bool WL = false>
 __global__ void k_env_ext(EnvParams p, StepOut o);
 __global__ void k_rank(EnvParams p, int64_t *rank);
 __global__ void k_target_means_lds(EnvParams p);
@@ -42,6 +45,8 @@ __global__ void k_act_obs(int P, int V, int policy, const float *obs, int32_t *a
 void big_geometry(int *nt, int *spt_max);
 void launch_big_env(int spt, bool one, int n_env, size_t lds, hipStream_t s, const EnvParams &p,
                     const StepOut &o);
+void launch_big_env_wl(int spt, bool one, int n_env, size_t lds, hipStream_t s,
+                       const EnvParams &p, const StepOut &o);  // vmp_kernels_wl.hip
 int big_occupancy(int spt, size_t lds, int *static_lds);
 
 int64_t quiet_violations_take();

@@ -48,16 +48,6 @@ int64_t quiet_violations_take() {
 #endif
 }
 
-template <bool ONE>
-static void launch_big_one(int spt, int n_env, size_t lds, hipStream_t s, const EnvParams &p,
-                           const StepOut &o) {
-  const dim3 grid(n_env), block(kBigNT);
-  if (spt == 4) hipLaunchKernelGGL((k_env_big<4, ONE>), grid, block, lds, s, p, o);
-  else if (spt == 8) hipLaunchKernelGGL((k_env_big<8, ONE>), grid, block, lds, s, p, o);
-  else if (spt == 16) hipLaunchKernelGGL((k_env_big<16, ONE>), grid, block, lds, s, p, o);
-  else
-  hipLaunchKernelGGL((k_env_big<kBigMaxSPT, ONE>), grid, block, lds, s, p, o);
-}
 // host side: the block kernel's geometry and launcher (vmp_capi.cpp)
 void big_geometry(int *nt, int *spt_max) {
   *nt = kBigNT;
@@ -65,8 +55,8 @@ void big_geometry(int *nt, int *spt_max) {
 }
 void launch_big_env(int spt, bool one, int n_env, size_t lds, hipStream_t s, const EnvParams &p,
                     const StepOut &o) {
-  if (one) launch_big_one<true>(spt, n_env, lds, s, p, o);
-  else launch_big_one<false>(spt, n_env, lds, s, p, o);
+  if (one) launch_big_one<true, false>(spt, n_env, lds, s, p, o);
+  else launch_big_one<false, false>(spt, n_env, lds, s, p, o);
 }
 // workgroups per CU of the per-step block kernel at `lds` dynamic bytes, and
 // its static LDS

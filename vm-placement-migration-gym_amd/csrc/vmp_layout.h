@@ -99,7 +99,10 @@ struct EnvParams {
   int64_t limit;          // eval_steps if eval_mode else training_steps
   int64_t M2;             // 2 * max(training_steps, eval_steps)
   double beta, seq_lo, seq_range;
-  const PoisConst *pois;  // device copy: [0] arrivals, [1] service lengths
+  // device copy: [0] arrivals, [1] service lengths, one pair for every env;
+  // once the handle has a per-env workload (vmp_set_workload) [N][2], env e's
+  // pair at pois + 2 e, read by the WL = true instantiations of the step kernels
+  const PoisConst *pois;
   uint64_t *stamps;       // [N][8] phase clocks (diagnostic builds only)
   uint32_t *vmw;          // [N][vm_pitch(V)] (slot words | time words per 64-slot block)
   double *pm;

@@ -13,8 +13,8 @@ POLICIES = {"firstfit": 0, "bestfit": 1}
 
 EXPORTS = (
     "vmp_abi_version", "vmp_last_error", "vmp_create", "vmp_destroy", "vmp_set_stream",
-    "vmp_set_eval", "vmp_dims", "vmp_reset", "vmp_step", "vmp_heuristic_act",
-    "vmp_heuristic_act_obs",
+    "vmp_set_eval", "vmp_dims", "vmp_set_workload", "vmp_get_workload", "vmp_reset", "vmp_step",
+    "vmp_heuristic_act", "vmp_heuristic_act_obs",
     "vmp_heuristic_step", "vmp_rollout_heuristic", "vmp_mask", "vmp_mask_bool", "vmp_get_obs",
     "vmp_get_counters", "vmp_get_stats", "vmp_get_state", "vmp_get_rank", "vmp_gae",
     "vmp_policy_head", "vmp_policy_head_backward", "vmp_policy_head_backward_bf16",
@@ -77,6 +77,8 @@ def lib():
         "vmp_set_stream": (ctypes.c_int, [P, P]),
         "vmp_set_eval": (ctypes.c_int, [P, i32]),
         "vmp_dims": (ctypes.c_int, [P, P, P, P, P, P]),
+        "vmp_set_workload": (ctypes.c_int, [P, P, P]),
+        "vmp_get_workload": (ctypes.c_int, [P, P, P]),
         "vmp_reset": (ctypes.c_int, [P, P, P, P]),
         "vmp_step": (ctypes.c_int, [P, P, P, P, P, P]),
         "vmp_step_mask": (ctypes.c_int, [P, P, P, P, P, P, P]),
@@ -127,7 +129,7 @@ def lib():
         if f is None:
             raise VmpError(f"libvmp lacks {name}")
         f.restype, f.argtypes = res, args
-    if L.vmp_abi_version() != 11:
+    if L.vmp_abi_version() != 12:
         raise VmpError("libvmp ABI mismatch")
     _lib = L
     return L

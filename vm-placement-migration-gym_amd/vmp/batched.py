@@ -26,7 +26,8 @@ REC_BINS = 1001
 
 
 class BatchedVmEnv:
-    def __init__(self, config: Config, n_envs: int, seeds=None, device="cuda", seed_stride=4):
+    def __init__(self, config: Config, n_envs: int, seeds=None, device="cuda", seed_stride=4,
+                 arrival_rate=None, service_length=None):
         if not torch.cuda.is_available():
             raise VmpError("BatchedVmEnv needs a HIP device (MI355X); no CPU fallback exists")
         self.config = config
@@ -52,6 +53,12 @@ class BatchedVmEnv:
                                    seeds.ctypes.data_as(ctypes.c_void_p), self.device.index,
                                    ctypes.byref(h)))
         self._h = h
+        if arrival_rate is not None or service_length is not None:
+            try:
+                self.set_workload(arrival_rate, service_length)
+            except Exception:
+                self.close()
+                raise
 
     # ------------------------------------------------------------ plumbing
     def _bind(self):
@@ -81,6 +88,40 @@ class BatchedVmEnv:
         """VmEnv.eval (env.py:105-106): switches the termination limit to eval_steps."""
         self.eval_mode = bool(mode)
         check(lib().vmp_set_eval(self._bind(), int(self.eval_mode)))
+
+    def _per_env(self, x, name):
+        if x is None:
+            return None
+        if isinstance(x, torch.Tensor):
+            x = x.detach().cpu().numpy()
+        a = np.asarray(x, dtype=np.float64)
+        if a.ndim == 0:
+            a = np.full(self.n_envs, float(a))
+        if a.shape != (self.n_envs,):
+            raise ValueError(f"{name} must be a scalar or have n_envs = {self.n_envs} entries")
+        return np.ascontiguousarray(a)
+
+    def set_workload(self, arrival_rate=None, service_length=None):
+        """Per-env workload (vmp_set_workload): env i draws its arrivals from
+        Poisson(arrival_rate[i]) and its planned runtimes from
+        Poisson(service_length[i]) + 1 from its next step on. Scalars or
+        array-likes of n_envs; None keeps that quantity. A graph captured before
+        the first call must be recaptured; later calls keep graphs valid."""
+        h = self._bind()
+        a = self._per_env(arrival_rate, "arrival_rate")
+        s = self._per_env(service_length, "service_length")
+        pa = None if a is None else a.ctypes.data_as(ctypes.c_void_p)
+        ps = None if s is None else s.ctypes.data_as(ctypes.c_void_p)
+        with torch.cuda.device(self.device):
+            check(lib().vmp_set_workload(h, pa, ps))
+
+    def workload(self):
+        """(arrival_rate, service_length) of every env as numpy f64 [n_envs]
+        (the config's values for an env never given a workload)."""
+        a, s = np.empty(self.n_envs, np.float64), np.empty(self.n_envs, np.float64)
+        check(lib().vmp_get_workload(self._bind(), a.ctypes.data_as(ctypes.c_void_p),
+                                     s.ctypes.data_as(ctypes.c_void_p)))
+        return a, s
 
     def reset(self, seeds=None, mask=None, obs=True):
         """reset(seed) for every env (or those where mask is true). seeds=None is
@@ -251,7 +292,8 @@ class BatchedVmEnv:
         """The whole batched env state (vmp_snapshot: PCG64 streams, counters,
         PM and VM words) as a device u8 tensor; `restore` on an env of the same
         config and n_envs continues bit-exactly from here. torch.save it for a
-        resumable run."""
+        resumable run (SURVEY §5). An env given a per-env workload appends it;
+        such a snapshot restores only into an env with the same workload."""
         h = self._bind()
         n = ctypes.c_int64()
         check(lib().vmp_snapshot_bytes(h, ctypes.byref(n)))

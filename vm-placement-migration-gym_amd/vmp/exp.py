@@ -6,6 +6,7 @@ comes back to the host. This replaces the reference's process fan-out
 (exp.py:1-2, 8 processes of one env each) and its per-step host Record.
 
     python -m vmp.exp suspension --out data.csv            # heuristic rows
+    python -m vmp.exp suspension --merge                   # one handle per agent, per-env workload
     python -m vmp.exp suspension --agents ppo --weights w.pt --out ppo.csv
     python -m vmp.exp performance --loads 1.0,0.6          # exp_performance.py summary
     python -m vmp.exp performance_small                    # exp_performance_small.py
@@ -79,24 +80,67 @@ class _RecordedRollout:
             self.env.rollout(self.policy, k % self.g)
 
 
+HEURISTICS = ("firstfit", "bestfit")
+WORKLOAD_KEYS = ("arrival_rate", "service_length")
+
+
+def merge_groups(cells, cfgs, merge=True):
+    """Which cells share one handle: a list of lists of cell indices, in order
+    of first appearance. Without `merge` every cell is its own group. With it,
+    heuristic cells of the same agent whose configs differ only in
+    arrival_rate / service_length (and the config seed, which the explicit
+    per-cell seeds override) form one group: their seeds become the envs of one
+    handle with a per-env workload. PPO cells, and cells that differ in
+    anything else, stay alone."""
+    groups, by_key = [], {}
+    for i, (cell, cfg) in enumerate(zip(cells, cfgs)):
+        if cell.agent != "ppo" and cell.agent not in HEURISTICS:
+            raise ValueError(f"agent {cell.agent!r} has no batched GPU path")
+        if not merge or cell.agent == "ppo":
+            groups.append([i])
+            continue
+        rest = tuple(sorted((k, repr(v)) for k, v in cfg.items()
+                            if k not in WORKLOAD_KEYS and k != "seed"))
+        key = (cell.agent, rest)
+        if key in by_key:
+            by_key[key].append(i)
+        else:
+            by_key[key] = [i]
+            groups.append(by_key[key])
+    return groups
+
+
 def run_cells(cells, make_config=None, eval_steps=None, chunk=2000, device="cuda:0",
-              graph_steps=100):
+              graph_steps=100, merge=False):
     """Evaluate every cell (Base.test per seed, base.py:63-118) for its eval_steps
     and return one list of Record summaries per cell (one dict per seed). All
     seeds of a cell are the envs of one handle, so the recorder's cross-env sums
     (VMP_REC_XMEM) span exactly the cell's seeds. Heuristic cells replay a
-    captured graph of graph_steps recorded steps (0 = plain launches)."""
-    envs, agents, streams, steps = [], [], [], []
+    captured graph of graph_steps recorded steps (0 = plain launches).
+    merge=True: the cells of one merge_groups group are the envs of ONE handle
+    (their seeds concatenated, each env at its cell's arrival rate and service
+    length), with one recorder and one captured rollout; the return value keeps
+    its shape, except that `_xmem` (a sum over a handle's envs) is NaN."""
+    cfgs = []
     for cell in cells:
         cfg = dict(cell.cfg) if cell.cfg is not None else make_config(cell.load, cell.service_length)
         if eval_steps is not None:
             cfg["eval_steps"] = int(eval_steps)
+        cfgs.append(cfg)
+    groups = merge_groups(cells, cfgs, merge)
+    envs, agents, streams, steps = [], [], [], []
+    for g in groups:
+        cell, cfg = cells[g[0]], cfgs[g[0]]
+        seeds = [int(s) for i in g for s in cells[i].seeds]
         s = torch.cuda.Stream(device=device)
         with torch.cuda.stream(s):
-            env = BatchedVmEnv(Config(**cfg), len(cell.seeds), seeds=list(cell.seeds),
-                               device=device)
+            env = BatchedVmEnv(Config(**cfg), len(seeds), seeds=seeds, device=device)
+            if len(g) > 1:  # before the capture: the first call moves the kernels' constants
+                env.set_workload(
+                    [cfgs[i]["arrival_rate"] for i in g for _ in cells[i].seeds],
+                    [cfgs[i]["service_length"] for i in g for _ in cells[i].seeds])
             env.eval(True)
-            env.reset(torch.tensor(list(cell.seeds), dtype=torch.int64))
+            env.reset(torch.tensor(seeds, dtype=torch.int64))
             env.record(True)  # before the graph capture, so replays are recorded too
             agent = None
             if cell.agent == "ppo":
@@ -105,34 +149,40 @@ def run_cells(cells, make_config=None, eval_steps=None, chunk=2000, device="cuda
                 ag.load_model(cell.weights)
                 ag.eval(True)
                 agent = ActStepGraph(ag, warmup=0)
-            elif cell.agent not in ("firstfit", "bestfit"):
-                raise ValueError(f"agent {cell.agent!r} has no batched GPU path")
             elif graph_steps:
                 agent = _RecordedRollout(env, cell.agent, int(graph_steps))
         envs.append(env)
         agents.append(agent)
         streams.append(s)
         steps.append(int(cfg["eval_steps"]))
-    done = [0] * len(cells)
+    done = [0] * len(groups)
     while any(d < t for d, t in zip(done, steps)):
-        for i, (cell, env, agent, s) in enumerate(zip(cells, envs, agents, streams)):
+        for i, (g, env, agent, s) in enumerate(zip(groups, envs, agents, streams)):
             k = min(chunk, steps[i] - done[i])
             if k <= 0:
                 continue
             with torch.cuda.stream(s):
                 if agent is None:
-                    env.rollout(cell.agent, k)
+                    env.rollout(cells[g[0]].agent, k)
                 elif isinstance(agent, _RecordedRollout):
                     agent.run(k)
                 else:
                     for _ in range(k):
                         agent.replay()
             done[i] += k
-    out = []
-    for env, s in zip(envs, streams):
+    out = [None] * len(cells)
+    for g, env, s in zip(groups, envs, streams):
         with torch.cuda.stream(s):
-            out.append(env.record_summary())
+            summ = env.record_summary()
         env.close()
+        at = 0
+        for i in g:
+            out[i] = summ[at:at + len(cells[i].seeds)]
+            at += len(cells[i].seeds)
+    if merge:
+        for summ in out:
+            for d in summ:
+                d["_xmem"] = float("nan")
     return out
 
 
@@ -147,9 +197,10 @@ def suspension_row(cell, summaries):
 
 
 def suspension_sweep(agents=("firstfit", "bestfit"), loads=None, lengths=None, seeds=(0,),
-                     weights=None, eval_steps=None):
+                     weights=None, eval_steps=None, merge=False):
     """The exp_suspension.py grid (load 1.0 x service lengths 100..3900 step 200,
-    then service length 1000 x loads 0.2..1.0) for the given agents."""
+    then service length 1000 x loads 0.2..1.0) for the given agents. merge=True
+    runs each heuristic agent's whole grid as the envs of one handle (run_cells)."""
     if lengths is None:
         lengths = list(range(100, 4100, 200))
     if loads is None:
@@ -158,7 +209,7 @@ def suspension_sweep(agents=("firstfit", "bestfit"), loads=None, lengths=None, s
              for sr in lengths for a in agents]
     cells += [Cell(a, float(ld), 1000, tuple(seeds), weights if a == "ppo" else None)
               for ld in loads for a in agents]
-    res = run_cells(cells, suspension_config, eval_steps=eval_steps)
+    res = run_cells(cells, suspension_config, eval_steps=eval_steps, merge=merge)
     return [suspension_row(c, r) for c, r in zip(cells, res)]
 
 
@@ -215,7 +266,10 @@ def performance_row(cell, summaries):
         f("_mean_pending"), f("_waiting"), f("_mean_slowdown"))
 
 
-def performance_sweep(cells, eval_steps=None):
+def performance_sweep(cells, eval_steps=None, merge=False):
+    if merge:  # Memory Variance needs the recorder's sums over exactly a cell's seeds
+        raise ValueError("performance_sweep cannot merge cells: its Memory Variance column "
+                         "is a cross-env sum over one handle's envs (_xmem)")
     res = run_cells(cells, eval_steps=eval_steps)
     return [performance_row(c, r) for c, r in zip(cells, res)]
 
@@ -324,6 +378,8 @@ def main(argv=None):
     ap.add_argument("--reward", default=None,
                     help="reward function(s): performance (default ut), reward (default wr,ut,kl)")
     ap.add_argument("--eval-steps", type=int, default=None)
+    ap.add_argument("--merge", action="store_true",
+                    help="suspension: one handle per heuristic agent, a per-env workload per cell")
     ap.add_argument("--out", default=None)
     a = ap.parse_args(argv)
     agents = a.agents.split(",")
@@ -334,7 +390,7 @@ def main(argv=None):
         rows = suspension_sweep(
             agents=agents, loads=loads,
             lengths=None if a.lengths is None else [int(x) for x in a.lengths.split(",")],
-            seeds=seeds or [0], weights=a.weights, eval_steps=a.eval_steps)
+            seeds=seeds or [0], weights=a.weights, eval_steps=a.eval_steps, merge=a.merge)
     elif a.experiment in ("performance", "performance_small"):
         header = PERFORMANCE_HEADER
         small = a.experiment == "performance_small"
@@ -342,7 +398,7 @@ def main(argv=None):
         cells = [performance_cell(ag, "ppo-" + reward if ag == "ppo" else ag, ld, reward,
                                   a.weights if ag == "ppo" else None, small, seeds)
                  for ld in (loads or [1.0]) for ag in agents]
-        rows = performance_sweep(cells, eval_steps=a.eval_steps)
+        rows = performance_sweep(cells, eval_steps=a.eval_steps, merge=a.merge)
     elif a.experiment == "reward":
         header = REWARD_HEADER
         rewards = a.reward.split(",") if a.reward else ["wr", "ut", "kl"]

@@ -76,6 +76,26 @@ class PPOConfig:
     kl_lookahead: bool = True          # step before the KL early-stop flag reaches the host,
                                        # roll back on a break (same accepted steps)
     seed_stride: int = 4               # env/episode reset seed spacing
+    # (lo, hi): every episode each env trains at its own load drawn uniformly in
+    # [lo, hi] (episode_loads), through the env's per-env arrival rate; None:
+    # every env keeps the config's arrival_rate
+    load_range: tuple = None
+
+
+def load_arrival_rate(pms, service_length, load):
+    """The reference's definition of load (exp_performance.py:20-33, unrounded):
+    the arrival rate at which `load` of the PMs' capacity is requested."""
+    return pms / 0.55 / service_length * load
+
+
+def episode_loads(seed, episode, rank, n_envs, load_range):
+    """The loads of a rank's envs in `episode`: n_envs uniform draws in
+    [lo, hi] from a numpy generator seeded with (env config seed, episode, rank)."""
+    lo, hi = (float(x) for x in load_range)
+    if not 0 <= lo <= hi:
+        raise ValueError(f"load_range must satisfy 0 <= lo <= hi, got {load_range!r}")
+    rng = np.random.default_rng([int(seed), int(episode), int(rank)])
+    return rng.uniform(lo, hi, int(n_envs))
 
 
 def ortho_init(layer, scale=np.sqrt(2)):
@@ -736,8 +756,15 @@ class PPOTrainer:
         gi = self.rank * self.N + torch.arange(self.N, device=self.dev, dtype=torch.int64)
         return int(self.env.config.seed) + int(self.cfg.seed_stride) * (episode * n_glob + gi)
 
+    def _episode_loads(self, episode):
+        return episode_loads(self.env.config.seed, episode, self.rank, self.N, self.cfg.load_range)
+
     def _start_episode(self, out_obs):
         self.env.eval(False)
+        if self.cfg.load_range is not None:
+            c = self.env.config
+            self.env.set_workload(arrival_rate=load_arrival_rate(
+                c.pms, c.service_length, self._episode_loads(self.episode)))
         out_obs.copy_(self.env.reset(self._episode_seeds(self.episode)))
         self.ep_t = 0
         self.ep_ret.zero_()
