@@ -8,6 +8,7 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "vmp_carve.h"
 #include "vmp_dev.h"
 #include "vmp_np_sort.h"
 
@@ -23,8 +24,8 @@ namespace vmp {
 // in flip(argsort(cpu + memory)) with numpy's scalar introsort tie order
 // (wave_aquicksort). One wave per env; the waiting VMs are
 // taken in index order, one PM scan (P/64 compares per lane) each. LDS:
-// cpu, memory, keys f32[P], order u16[P], sort stack i32[256] + scratch
-// u16[2P]. Not the hot path (the Base.test loop and the bench act on the
+// cpu, memory, keys f32[P], sort stack i32[kSortStackWords] + scratch u16[2P],
+// order u16[P] (act_obs_lds, vmp_carve.h). Not the hot path (the Base.test loop and the bench act on the
 // env's own state, k_env); this is the contract of act(observation).
 __device__ __forceinline__ int act_obs_bf(const float LDSP *fc, const float LDSP *fm,
                                           float LDSP *key, uint16_t LDSP *ord,
@@ -70,7 +71,7 @@ __device__ __forceinline__ int act_obs_bf(const float LDSP *fc, const float LDSP
   }
   const int hi = P - above - 1, lo = P - above - eq;
   wsync();
-  wave_aquicksort(KeyArr{key}, ord, P, stk, lo, hi, reinterpret_cast<uint16_t LDSP *>(stk + 256));
+  wave_aquicksort(KeyArr{key}, ord, P, stk, lo, hi, reinterpret_cast<uint16_t LDSP *>(stk + kSortStackWords));
   wsync();
   for (int b = hi; b >= lo; b -= 64) {  // visiting order: descending positions
     const int pos = b - lane;
@@ -88,7 +89,7 @@ __global__ __launch_bounds__(64) void k_act_obs(int P, int V, int policy, const 
   float LDSP *fm = fc + P;
   float LDSP *key = fm + P;
   int32_t LDSP *stk = reinterpret_cast<int32_t LDSP *>(key + P);
-  uint16_t LDSP *ord = reinterpret_cast<uint16_t LDSP *>(stk + 256 + P);  // after the scratch
+  uint16_t LDSP *ord = reinterpret_cast<uint16_t LDSP *>(stk + kSortStackWords + P);  // after the scratch
   const int lane = lane_id(), e = blockIdx.x;
   const int D = 3 * V + 2 * P;
   const float *o = obs + (int64_t)e * D;

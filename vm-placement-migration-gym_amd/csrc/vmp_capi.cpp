@@ -1,94 +1,22 @@
 // vmp_capi.cpp — extern "C" entry points of libvmp.so (declared in include/vmp.h).
-// Host-side: argument checks, device allocation, per-config constants
-// (Poisson setup evaluated with glibc exactly as numpy's C code does), LDS
-// carve-out, and kernel dispatch on the handle's stream.
+// Argument checks, device allocation and kernel dispatch on the handle's stream
+// (error text, counted allocations, Poisson setup: vmp_host.h; LDS carve: vmp_carve.h).
 #include <hip/hip_runtime.h>
 
-#include <atomic>
-
 #include <cmath>
-#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <string>
 #include <vector>
 
 #include "../../include/vmp.h"
+#include "vmp_carve.h"
+#include "vmp_host.h"
 #include "vmp_kernels.h"
 #include "vmp_layout.h"
 #include "vmp_record.h"
 
 using namespace vmp;
-
-namespace {
-thread_local std::string g_err;
-
-int fail(int code, const std::string &msg) {
-  g_err = msg;
-  return code;
-}
-
-#define HIP_TRY(expr)                                                              \
-  do {                                                                             \
-    hipError_t _e = (expr);                                                        \
-    if (_e != hipSuccess)                                                          \
-      return fail(_e == hipErrorOutOfMemory ? VMP_EOOM : VMP_EDEVICE,              \
-                  std::string(#expr) + ": " + hipGetErrorString(_e));              \
-  } while (0)
-
-// Device allocations of the handle go through here, so the failure paths can
-// be exercised (vmp_debug_fail_alloc: the n-th allocation from now fails as
-// out-of-memory; tests/test_sanitizers_cpu.py, tests/native/capi_faults.cpp).
-// g_live counts the library's live device allocations (vmp_debug_live_allocs),
-// so a leak on a failure path is seen exactly, whatever the runtime caches.
-std::atomic<int64_t> g_fail_alloc{0};
-std::atomic<int64_t> g_live{0};
-template <class T>
-hipError_t dev_malloc(T **p, size_t bytes) {
-  int64_t n = g_fail_alloc.load();
-  while (n > 0 && !g_fail_alloc.compare_exchange_weak(n, n - 1)) {
-  }
-  if (n == 1) {
-    *p = nullptr;
-    return hipErrorOutOfMemory;
-  }
-  const hipError_t e = hipMalloc(reinterpret_cast<void **>(p), bytes);
-  if (e == hipSuccess && *p) g_live++;
-  else *p = nullptr;
-  return e;
-}
-void dev_free(void *p) {
-  if (!p) return;
-  (void)hipFree(p);
-  g_live--;
-}
-
-// random_loggam (numpy distributions.c), host copy for the PTRS table.
-double loggam_host(double x) {
-  static const double a[10] = {8.333333333333333e-02, -2.777777777777778e-03,
-                               7.936507936507937e-04, -5.952380952380952e-04,
-                               8.417508417508418e-04, -1.917526917526918e-03,
-                               6.410256410256410e-03, -2.955065359477124e-02,
-                               1.796443723688307e-01, -1.39243221690590e+00};
-  if (x == 1.0 || x == 2.0) return 0.0;
-  int64_t n = (x < 7.0) ? (int64_t)(7 - x) : 0;
-  double x0 = x + n;
-  double x2 = (1.0 / x0) * (1.0 / x0);
-  double gl0 = a[9];
-  for (int k = 8; k >= 0; k--) {
-    gl0 *= x2;
-    gl0 += a[k];
-  }
-  double gl = gl0 / x0 + 0.5 * 1.8378770664093453e+00 + (x0 - 0.5) * std::log(x0) - x0;
-  if (x < 7.0)
-    for (int64_t k = 1; k <= n; k++) {
-      gl -= std::log(x0 - 1.0);
-      x0 -= 1.0;
-    }
-  return gl;
-}
-
-}  // namespace
 
 namespace vmp {
 // error reporting for the policy kernels (vmp_policy.hip) through vmp_last_error()
@@ -130,247 +58,38 @@ struct vmp_handle {
 
 namespace {
 
-// The constants of Poisson(lam) and the length tab_n of the loggam table its
-// PTRS draws index (entry k = loggam(k), the same for every lam); loggam_tab
-// is left null for the caller to point at a table of at least tab_n entries.
-void pois_consts(double lam, PoisConst &c) {
-  std::memset(&c, 0, sizeof(c));
-  c.lam = lam;
-  if (lam == 0) {
-    c.kind = 0;
-  } else if (lam < 10) {
-    c.kind = 1;
-    c.enlam = std::exp(-lam);
-  } else {
-    c.kind = 2;
-    double slam = std::sqrt(lam);
-    c.loglam = std::log(lam);
-    c.b = 0.931 + 2.53 * slam;
-    c.a = -0.059 + 0.02483 * c.b;
-    c.invalpha = 1.1239 + 1.1328 / (c.b - 3.4);
-    c.vr = 0.9277 - 3.6224 / (c.b - 2);
-    c.log_invalpha = std::log(c.invalpha);
-    int64_t n = (int64_t)(lam + 16.0 * slam + 64.0);
-    if (n > (1 << 22)) n = 1 << 22;
-    c.tab_n = (int32_t)n;
-  }
-}
-
-// A device table loggam(k), k in [0, n).
-int make_loggam_tab(int64_t n, double **dev_tab) {
-  std::vector<double> host_tab((size_t)n);
-  for (int64_t k = 0; k < n; k++) host_tab[(size_t)k] = loggam_host((double)k);
-  HIP_TRY(dev_malloc(dev_tab, sizeof(double) * n));
-  const hipError_t e = hipMemcpy(*dev_tab, host_tab.data(), sizeof(double) * n, hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
-    dev_free(*dev_tab);
-    *dev_tab = nullptr;
-    return fail(VMP_EDEVICE, std::string("loggam table copy: ") + hipGetErrorString(e));
-  }
-  return VMP_OK;
-}
-
-int setup_pois(double lam, PoisConst &c, double **dev_tab) {
-  pois_consts(lam, c);
-  if (c.kind == 2) {
-    const int rc = make_loggam_tab(c.tab_n, dev_tab);
-    if (rc != VMP_OK) return rc;
-    c.loggam_tab = *dev_tab;
-  }
-  return VMP_OK;
-}
-
-inline int64_t align16(int64_t x) { return (x + 15) & ~(int64_t)15; }
-
-// Max recursion depth of numpy's pairwise split for n <= V (kernel limit 5).
-int pw_depth(int n) {
-  if (n <= 128) return 0;
-  int n2 = n / 2;
-  n2 -= n2 % 8;
-  int a = pw_depth(n2), b = pw_depth(n - n2);
-  return 1 + (a > b ? a : b);
-}
-int pw_leaves(int n) {
-  if (n <= 128) return 1;
-  int n2 = n / 2;
-  n2 -= n2 % 8;
-  return pw_leaves(n2) + pw_leaves(n - n2);
-}
-
-void carve_big(vmp_handle *h);
-
-void carve(vmp_handle *h) {
-  EnvParams &p = h->prm;
-  const int64_t P = h->P, V = h->V;
-  int max_leaves = 1;
-  bool deep = (V > 1928 || P > 1928);  // only deeper recursions use the LDS plan
-  if (deep)
-    for (int n = 0; n <= V || n <= P; n++) {
-      int l = pw_leaves(n);
-      if (l > max_leaves) max_leaves = l;
-    }
-  p.NW = (int32_t)((P + 63) / 64);
-  p.n_leaf = deep ? max_leaves + 8 : 1;
-  int64_t off = 0;
-  p.off_hdr = (int32_t)off;
-  off = align16(off + (int64_t)sizeof(EnvHdr));
-  p.off_pm = (int32_t)off;
-  off = align16(off + 16 * P);           // cpu, mem f64
-  p.off_fpm = (int32_t)off;
-  off = align16(off + 12 * P);           // fcpu, fmem f32 (+ P spare: the wave kernel's
-  p.off_thr = (int32_t)off;              // measured layout; BF keys are formed on the fly)
-  off = align16(off + 2 * P);            // tc, tm u8
-  p.fmem_off = (int32_t)P;
-  p.tm_off = (int32_t)P;
-  p.off_ord = (int32_t)off;
-  off = align16(off + 2 * P);            // BF visiting order u16
-  p.off_bits = (int32_t)off;  // any-fit table (u32[128]); after the heuristic: NULL list + accepted sizes
-  off = align16(off + (4 * V > 512 ? 4 * V : 512));
-  p.off_stage = (int32_t)off;
-  off = align16(off + 8 * 16);           // reduction results + draw bookkeeping
-  // ccomp, mcomp u8 (stats, after the action phase) share their region with
-  // the BF introsort stacks + partition lists (action phase only)
-  p.off_ccomp = (int32_t)off;
-  p.off_sort = (int32_t)off;
-  off = align16(off + (2 * V > 4 * 256 + 4 * P ? 2 * V : 4 * 256 + 4 * P));
-  // the LDS plan of the pairwise sums exists only for n > 1928 (wave_pw_sum)
-  p.off_leaf = (int32_t)off;
-  if (deep) off = align16(off + 8 * (int64_t)p.n_leaf + 4 * 192);  // lo, len, lane-0 stack
-  p.off_leafval = (int32_t)off;
-  if (deep) off = align16(off + 8 * (2 * (int64_t)p.n_leaf + 64));  // leaf sums + value stack
-  // changed-PM bitmap (bit i: double i of cpu[P] | memory[P] was written this
-  // launch): only those PM words are stored back
-  p.off_pdirty = (int32_t)off;
-  off = align16(off + 8 * ((2 * P + 63) / 64));
-  p.off_acc = p.off_bits + (int32_t)(2 * V);  // after the NULL list
-  p.acc_cap = (int32_t)V;
-  p.ccomp_cap = (int32_t)V;
-  p.off_ev = 0;  // k_env_big only
-  p.off_pre = (int32_t)off;   // per-launch random draws follow (launch_env)
-  p.lds_wave_bytes = (int32_t)off;
-  if (h->big) carve_big(h);
-}
-
-// k_env_big's carve, sized for two workgroups per CU at P1000 / V10000 (≤ 80 KB
-// with the VM words): the regions of the action phase and of the tail share
-// one union. Heuristic side: the f32 view fcpu/fmem, thresholds tc/tm, the BF
-// tie sort's order and stacks. Tail side: the pairwise-sum LDS plan, the
-// event lists, the accepted sizes (≤ 512 in LDS) and the existing-VM sizes
-// (as many as the rest of the union holds). Steps with more accepted or
-// existing VMs than that use the handle's HBM spill (p.bigscr).
-void carve_big(vmp_handle *h) {
-  EnvParams &p = h->prm;
-  const int64_t P = h->P, V = h->V;
-  const bool deep = p.n_leaf > 1;
-  int64_t off = 0;
-  p.off_hdr = 0;
-  off = align16((int64_t)sizeof(EnvHdr));
-  p.off_pm = (int32_t)off;
-  off = align16(off + 16 * P);
-  p.off_stage = (int32_t)off;
-  off = align16(off + 8 * 16);
-  p.off_pdirty = (int32_t)off;
-  off = align16(off + 8 * ((2 * P + 63) / 64));
-  const int64_t u0 = off;
-  // heuristic side
-  p.off_fpm = (int32_t)off;
-  off = align16(off + 8 * ((P + 3) & ~3));  // fcpu, fmem f32, 16-B aligned rows (BF keys are formed on the fly)
-  p.off_thr = (int32_t)off;
-  off = align16(off + 2 * align16(P));      // tc, tm u8, 16-B aligned rows (big_choose)
-  p.fmem_off = (int32_t)((P + 3) & ~3);
-  p.tm_off = (int32_t)align16(P);
-  p.off_ord = (int32_t)off;
-  off = align16(off + 2 * P);
-  p.off_sort = (int32_t)off;
-  off = align16(off + 4 * 256 + 4 * P);
-  const int64_t heur_end = off;
-  p.off_bits = p.off_fpm;  // the wave kernel's any-fit table / NULL list: unused here
-  // tail side
-  off = u0;
-  p.off_leaf = (int32_t)off;
-  if (deep) off = align16(off + 8 * (int64_t)p.n_leaf + 4 * 192);
-  p.off_leafval = (int32_t)off;
-  if (deep) off = align16(off + 8 * (2 * (int64_t)p.n_leaf + 64));
-  p.off_ev = (int32_t)off;
-  off = align16(off + 512 * (4 + 4 + 1));
-  p.acc_cap = (int32_t)(V < kBigAccLds ? V : kBigAccLds);
-  p.off_acc = (int32_t)off;
-  off = align16(off + 2 * (int64_t)p.acc_cap);
-  p.off_ccomp = (int32_t)off;
-  int64_t cap = (heur_end - off) / 2;
-  const int64_t cap_min = V < 1024 ? V : 1024;
-  if (cap < cap_min) cap = cap_min;
-  if (cap > V) cap = V;
-  p.ccomp_cap = (int32_t)cap;
-  off = align16(off + 2 * cap);
-  if (off < heur_end) off = heur_end;
-  p.off_pre = (int32_t)off;
-  p.lds_wave_bytes = (int32_t)off;
-}
-
-// WL: the handle has a per-env workload (the kernels of vmp_kernels_wl.hip)
-template <bool WL>
-void launch_ext(int need, dim3 grid, dim3 block, size_t lds, hipStream_t s, const EnvParams &p,
-                const StepOut &o) {
-  if (need <= 1) hipLaunchKernelGGL((k_env_ext<1, WL>), grid, block, lds, s, p, o);
-  else if (need <= 2) hipLaunchKernelGGL((k_env_ext<2, WL>), grid, block, lds, s, p, o);
-  else if (need <= 4) hipLaunchKernelGGL((k_env_ext<4, WL>), grid, block, lds, s, p, o);
-  else if (need <= 8) hipLaunchKernelGGL((k_env_ext<8, WL>), grid, block, lds, s, p, o);
-  else hipLaunchKernelGGL((k_env_ext<16, WL>), grid, block, lds, s, p, o);
-}
-
-template <bool ONE, bool WL>
-void launch_vpt(int need, dim3 grid, dim3 block, size_t lds, hipStream_t s, const EnvParams &p,
-                const StepOut &o) {
-  if (need <= 1) hipLaunchKernelGGL((k_env<1, ONE, WL>), grid, block, lds, s, p, o);
-  else if (need <= 2) hipLaunchKernelGGL((k_env<2, ONE, WL>), grid, block, lds, s, p, o);
-  else if (need <= 4) hipLaunchKernelGGL((k_env<4, ONE, WL>), grid, block, lds, s, p, o);
-  else if (need <= 8) hipLaunchKernelGGL((k_env<8, ONE, WL>), grid, block, lds, s, p, o);
-  else hipLaunchKernelGGL((k_env<16, ONE, WL>), grid, block, lds, s, p, o);
-}
-
-// k_env_big's shape: the fewest slots per thread that fit 384 threads, and the
-// thread count (whole waves). The block's VM words live in LDS (4 B per slot).
-void big_shape(int64_t V, int &spt, int &nt) {
-  int mx;
-  big_geometry(&nt, &mx);  // nt: the kernel's compile-time workgroup size (kBigNT)
-  spt = V <= 4 * nt ? 4 : V <= 8 * nt ? 8 : V <= 16 * nt ? 16 : mx;
+// The wave step kernel of VPT slot rows per lane: external actions, the
+// per-step launch or the fused rollout; wl: the handle has a per-env workload
+// (p.pois is [N][2]: the kernels of vmp_kernels_wl.hip)
+using EnvKernel = void (*)(EnvParams, StepOut);
+template <int VPT>
+EnvKernel env_kernel(bool ext, bool one, bool wl) {
+  if (ext) return wl ? k_env_ext<VPT, true> : k_env_ext<VPT, false>;
+  if (one) return wl ? k_env<VPT, true, true> : k_env<VPT, true, false>;
+  return wl ? k_env<VPT, false, true> : k_env<VPT, false, false>;
 }
 
 int launch_env(vmp_handle *h, const StepOut &o) {
   dim3 grid((h->N + kEnvWavesPerBlock - 1) / kEnvWavesPerBlock), block(64 * kEnvWavesPerBlock);
   EnvParams p = h->prm;
-  const bool wl = h->pois_env != nullptr;  // p.pois is [N][2]: the WL kernels
-  // per-launch region: speculative service draws (state + value) and arrivals
+  const bool wl = h->pois_env != nullptr;
+  const int spt = big_spt(h->V);
   p.scap = kSpecDraws;
-  const int64_t pre = 20 * (int64_t)p.scap + 4 * (int64_t)(o.k_steps > 0 ? o.k_steps : 1);
-  p.lds_wave_bytes = (int32_t)align16(p.off_pre + pre);
-  size_t lds = (size_t)p.lds_wave_bytes * kEnvWavesPerBlock;
-  if (!h->big && lds > 160 * 1024 - 2048) return fail(VMP_EINVAL, "config too large for the LDS carve");
-  if (h->big) {
-    // one workgroup per env; the VM words follow the wave carve
-    int spt, nt;
-    big_shape(h->V, spt, nt);
-    const size_t lds1 = (size_t)p.lds_wave_bytes + 4 * (size_t)spt * nt;
-    if (wl) launch_big_env_wl(spt, o.k_steps == 1, h->N, lds1, h->stream, p, o);
-    else launch_big_env(spt, o.k_steps == 1, h->N, lds1, h->stream, p, o);
-    HIP_TRY(hipGetLastError());
-    return VMP_OK;
+  p.lds_wave_bytes = launch_wave_bytes(p, o.k_steps);
+  const size_t lds = launch_lds(p, o.k_steps, h->big, spt);
+  if (!lds_fits(lds, h->big)) return fail(VMP_EINVAL, "config too large for the LDS carve");
+  if (h->big) {  // one workgroup per env
+    if (wl) launch_big_env_wl(spt, o.k_steps == 1, h->N, lds, h->stream, p, o);
+    else launch_big_env(spt, o.k_steps == 1, h->N, lds, h->stream, p, o);
+    return launched();
   }
-  const int need = (h->V + 63) / 64;
-  if (o.actions) {  // external actions: vmp_step, one step
-    if (o.k_steps != 1) return fail(VMP_EINVAL, "external actions take one step per launch");
-    if (wl) launch_ext<true>(need, grid, block, lds, h->stream, p, o);
-    else launch_ext<false>(need, grid, block, lds, h->stream, p, o);
-  } else if (o.k_steps == 1) {
-    if (wl) launch_vpt<true, true>(need, grid, block, lds, h->stream, p, o);
-    else launch_vpt<true, false>(need, grid, block, lds, h->stream, p, o);
-  } else {
-    if (wl) launch_vpt<false, true>(need, grid, block, lds, h->stream, p, o);
-    else launch_vpt<false, false>(need, grid, block, lds, h->stream, p, o);
-  }
-  HIP_TRY(hipGetLastError());
-  return VMP_OK;
+  // external actions: vmp_step, one step
+  if (o.actions && o.k_steps != 1) return fail(VMP_EINVAL, "external actions take one step per launch");
+  const int need = (h->V + 63) / 64;  // the fewest of 1 / 2 / 4 / 8 / 16 rows that hold V
+  const auto pick = need <= 1 ? env_kernel<1> : need <= 2 ? env_kernel<2> : need <= 4 ? env_kernel<4>
+                    : need <= 8 ? env_kernel<8> : env_kernel<16>;
+  hipLaunchKernelGGL(pick(o.actions != nullptr, o.k_steps == 1, wl), grid, block, lds, h->stream, p, o);
+  return launched();
 }
 
 StepOut empty_out() {
@@ -383,6 +102,11 @@ StepOut empty_out() {
 void refresh_params(vmp_handle *h) {
   h->prm.eval_mode = h->eval_mode;
   h->prm.limit = h->eval_mode ? h->cfg.eval_steps : h->cfg.training_steps;
+}
+
+int check_policy(int32_t policy) {
+  if (policy == VMP_POLICY_FIRSTFIT || policy == VMP_POLICY_BESTFIT) return VMP_OK;
+  return fail(VMP_EINVAL, "unknown policy");
 }
 
 }  // namespace
@@ -398,9 +122,7 @@ int vmp_create(const vmp_config *cfg, int32_t n_env, const int64_t *seeds, int32
                vmp_handle **out) {
   if (!cfg || !out || n_env <= 0 || !seeds) return fail(VMP_EINVAL, "null argument or n_env <= 0");
   if (cfg->pms < 1 || cfg->pms > 65533) return fail(VMP_EINVAL, "pms must be in [1, 65533]");
-  int big_nt, big_spt;
-  big_geometry(&big_nt, &big_spt);
-  if (cfg->vms < 1 || cfg->vms > big_nt * big_spt)
+  if (cfg->vms < 1 || cfg->vms > kBigNT * kBigMaxSPT)
     return fail(VMP_EINVAL, "vms must be in [1, 10240] on this build");
   if (cfg->reward_function < 0 || cfg->reward_function > 2)
     return fail(VMP_EINVAL, "Function does not exist: reward_function");  // env.py:156
@@ -419,25 +141,14 @@ int vmp_create(const vmp_config *cfg, int32_t n_env, const int64_t *seeds, int32
   h->A = cfg->allow_null_action ? cfg->pms + 2 : cfg->pms + 1;
   h->D = 3 * cfg->vms + 2 * cfg->pms;
   h->W32 = (h->A + 31) / 32;
-  {
-    const char *force = getenv("VMP_BIG_KERNEL");
-    h->big = cfg->vms > kMaxVPT * kWaveSize || (force && force[0] == '1');
-  }
+  const char *force = getenv("VMP_BIG_KERNEL");
+  h->big = cfg->vms > kMaxVPT * kWaveSize || (force && force[0] == '1');
   h->device = device;
   h->stream = nullptr;
   int rc = setup_pois(cfg->arrival_rate, h->arr, &h->lg_arr);
   if (rc == VMP_OK) rc = setup_pois(cfg->service_length, h->svc, &h->lg_svc);
-  if (rc != VMP_OK) {
-    const std::string msg = g_err;
-    vmp_destroy(h);  // frees whatever the first setup_pois allocated
-    return fail(rc, msg);
-  }
-  rc = create_rest(h, cfg, n_env, seeds);
-  if (rc != VMP_OK) {
-    const std::string msg = g_err;
-    vmp_destroy(h);
-    return fail(rc, msg);
-  }
+  if (rc == VMP_OK) rc = create_rest(h, cfg, n_env, seeds);
+  if (rc != VMP_OK) return fail_after(rc, [&] { vmp_destroy(h); });  // frees what was allocated
   *out = h;
   return VMP_OK;
 }
@@ -490,7 +201,8 @@ static int create_rest(vmp_handle *h, const vmp_config *cfg, int32_t n_env, cons
   p.vmw = h->vmw;
   p.pm = h->pm;
   p.hdr = h->hdr;
-  carve(h);
+  if (h->big) carve_big(h->P, h->V, p);
+  else carve_wave(h->P, h->V, p);
   if (h->big) {
     HIP_TRY(dev_malloc(&h->bigscr, (size_t)n_env * 4 * (size_t)h->V));
     p.bigscr = h->bigscr;
@@ -506,20 +218,10 @@ static int create_rest(vmp_handle *h, const vmp_config *cfg, int32_t n_env, cons
     HIP_TRY(hipMemset(h->stamps, 0, sizeof(uint64_t) * kStamps * (size_t)n_env));
     p.stamps = h->stamps;
   }
-  int maxn = h->V > h->P ? h->V : h->P;
-  int depth = 0;
-  for (int n = 0; n <= maxn; n++) depth = pw_depth(n) > depth ? pw_depth(n) : depth;
-  if (depth > 12)
+  if (pw_worst(h->V > h->P ? h->V : h->P).depth > 12)
     return fail(VMP_EINVAL, "config exceeds the pairwise-sum recursion depth of this build");
-  {
-    const int64_t per_env = p.lds_wave_bytes + 20 * kSpecDraws + 4 * kMaxStepsPerLaunch;
-    int spt = 0, nt = 0;
-    if (h->big) big_shape(h->V, spt, nt);
-    const int64_t need = h->big ? per_env + kBigStaticLds + 4 * (int64_t)spt * nt
-                                : per_env * kEnvWavesPerBlock + kEnvStaticLds;
-    if (need > 160 * 1024)
-      return fail(VMP_EINVAL, "config too large for the LDS carve of this build");
-  }
+  if (!carve_fits(p, h->big))
+    return fail(VMP_EINVAL, "config too large for the LDS carve of this build");
   refresh_params(h);
   int64_t *dseeds = nullptr;
   HIP_TRY(dev_malloc(&dseeds, sizeof(int64_t) * n_env));
@@ -537,18 +239,10 @@ static int create_rest(vmp_handle *h, const vmp_config *cfg, int32_t n_env, cons
 
 int vmp_destroy(vmp_handle *h) {
   if (!h) return VMP_OK;
-  dev_free(h->vmw);
-  dev_free(h->pm);
-  dev_free(h->hdr);
-  dev_free(h->lg_arr);
-  dev_free(h->lg_svc);
-  dev_free(h->scratch_bits);
-  dev_free(h->pois_dev);
-  dev_free(h->jump_dev);
-  dev_free(h->bigscr);
-  dev_free(h->stamps);
-  dev_free(h->pois_env);
-  dev_free(h->lg_shared);
+  for (void *q : {(void *)h->vmw, (void *)h->pm, (void *)h->hdr, (void *)h->lg_arr, (void *)h->lg_svc,
+                  (void *)h->scratch_bits, (void *)h->pois_dev, (void *)h->jump_dev, (void *)h->bigscr,
+                  (void *)h->stamps, (void *)h->pois_env, (void *)h->lg_shared})
+    dev_free(q);
   std::free(h->wl);
   std::free(h->wl_rec);
   vmp_record_enable(h, 0);
@@ -625,16 +319,15 @@ int vmp_set_workload(vmp_handle *h, const double *arrival_rate, const double *se
       }
     }
   }
-  if (rc != VMP_OK) {
-    const std::string msg = g_err;
-    dev_free(tab_new);
-    dev_free(dev_new);
-    if (first) {
-      std::free(wl_new);
-      std::free(rec_new);
-    }
-    return fail(rc, msg);
-  }
+  if (rc != VMP_OK)
+    return fail_after(rc, [&] {
+      dev_free(tab_new);
+      dev_free(dev_new);
+      if (first) {
+        std::free(wl_new);
+        std::free(rec_new);
+      }
+    });
   // commit. No queued launch reads the old table any more (synchronised above)
   if (tab_new) {
     dev_free(h->lg_shared);
@@ -688,12 +381,25 @@ int vmp_reset(vmp_handle *h, const int64_t *seeds, const uint8_t *env_mask, floa
   if (!h) return fail(VMP_EINVAL, "null handle");
   dim3 grid((h->N + kWavesPerBlock - 1) / kWavesPerBlock), block(64 * kWavesPerBlock);
   hipLaunchKernelGGL(k_reset, grid, block, 0, h->stream, h->prm, seeds, env_mask, obs);
-  HIP_TRY(hipGetLastError());
-  return VMP_OK;
+  return launched();
 }
 
-static int record_after(vmp_handle *h, const int32_t *act, const uint8_t *valid,
-                        const double *reward);
+// One step; with recording on, the recorder (vmp_record.hip) after it, on the
+// handle's scratch action / validity / reward where the caller passes none
+static int step_recorded(vmp_handle *h, StepOut o) {
+  if (!h->rec_on) return launch_env(h, o);
+  if (!o.actions && !o.act_out) o.act_out = h->rec_act;
+  if (!o.reward) o.reward = h->rec_reward;
+  if (!o.valid) o.valid = h->rec_valid;
+  if (const int rc = launch_env(h, o)) return rc;
+  RecArgs r = h->rec;
+  r.act = o.actions ? o.actions : o.act_out;
+  r.valid = o.valid;
+  r.reward = o.reward;
+  const size_t lds = (size_t)4 * ((h->P + 63) / 64) * sizeof(unsigned long long);
+  hipLaunchKernelGGL(k_record, dim3((h->N + 3) / 4), dim3(256), lds, h->stream, h->prm, r);
+  return launched();
+}
 
 int vmp_step(vmp_handle *h, const int32_t *actions, float *obs, double *reward, uint8_t *done,
              uint8_t *valid) {
@@ -711,19 +417,12 @@ int vmp_step_mask(vmp_handle *h, const int32_t *actions, float *obs, double *rew
   o.valid = valid;
   o.mask_bits = next_mask_bits;  // written from the post-step state, as vmp_mask would
   o.k_steps = 1;
-  if (h->rec_on) {
-    if (!o.reward) o.reward = h->rec_reward;
-    if (!o.valid) o.valid = h->rec_valid;
-  }
-  int rc = launch_env(h, o);
-  if (rc == VMP_OK && h->rec_on) rc = record_after(h, actions, o.valid, o.reward);
-  return rc;
+  return step_recorded(h, o);
 }
 
 int vmp_heuristic_act(vmp_handle *h, int32_t policy, int32_t *actions) {
   if (!h || !actions) return fail(VMP_EINVAL, "null handle or actions");
-  if (policy != VMP_POLICY_FIRSTFIT && policy != VMP_POLICY_BESTFIT)
-    return fail(VMP_EINVAL, "unknown policy");
+  if (const int rc = check_policy(policy)) return rc;
   StepOut o = empty_out();
   o.policy = policy;
   o.act_out = actions;
@@ -733,23 +432,20 @@ int vmp_heuristic_act(vmp_handle *h, int32_t policy, int32_t *actions) {
 
 int vmp_heuristic_act_obs(vmp_handle *h, int32_t policy, const float *obs, int32_t *actions) {
   if (!h || !obs || !actions) return fail(VMP_EINVAL, "null handle, obs or actions");
-  if (policy != VMP_POLICY_FIRSTFIT && policy != VMP_POLICY_BESTFIT)
-    return fail(VMP_EINVAL, "unknown policy");
-  const size_t lds = 18 * (size_t)h->P + 1024;  // cpu, memory, keys, order, sort stack
-  // the whole PM view in one workgroup's LDS (gfx950: 160 KB per workgroup)
-  if (lds > (size_t)160 * 1024) return fail(VMP_EINVAL, "act from observation supports P <= 9045");
+  if (const int rc = check_policy(policy)) return rc;
+  // the whole PM view in one workgroup's LDS
+  const size_t lds = act_obs_lds(h->P);
+  if (lds > (size_t)kCuLdsBytes) return fail(VMP_EINVAL, "act from observation supports P <= 9045");
   hipLaunchKernelGGL(k_act_obs, dim3(h->N), dim3(64), lds, h->stream, h->P, h->V, policy, obs,
                      actions);
-  HIP_TRY(hipGetLastError());
-  return VMP_OK;
+  return launched();
 }
 
 static int heuristic_step_impl(vmp_handle *h, int32_t policy, int32_t *actions_out, float *obs,
                                double *reward, uint8_t *done, uint8_t *valid,
                                int64_t *done_count) {
   if (!h) return fail(VMP_EINVAL, "null handle");
-  if (policy != VMP_POLICY_FIRSTFIT && policy != VMP_POLICY_BESTFIT)
-    return fail(VMP_EINVAL, "unknown policy");
+  if (const int rc = check_policy(policy)) return rc;
   StepOut o = empty_out();
   o.policy = policy;
   o.act_out = actions_out;
@@ -759,14 +455,7 @@ static int heuristic_step_impl(vmp_handle *h, int32_t policy, int32_t *actions_o
   o.done_count = done_count;
   o.valid = valid;
   o.k_steps = 1;
-  if (h->rec_on) {
-    if (!o.act_out) o.act_out = h->rec_act;
-    if (!o.reward) o.reward = h->rec_reward;
-    if (!o.valid) o.valid = h->rec_valid;
-  }
-  int rc = launch_env(h, o);
-  if (rc == VMP_OK && h->rec_on) rc = record_after(h, o.act_out, o.valid, o.reward);
-  return rc;
+  return step_recorded(h, o);
 }
 
 int vmp_heuristic_step(vmp_handle *h, int32_t policy, int32_t *actions_out, float *obs,
@@ -777,8 +466,7 @@ int vmp_heuristic_step(vmp_handle *h, int32_t policy, int32_t *actions_out, floa
 int vmp_rollout_heuristic(vmp_handle *h, int32_t policy, int32_t k_steps, double *rewards,
                           int64_t *done_count) {
   if (!h || k_steps < 1) return fail(VMP_EINVAL, "null handle or k_steps < 1");
-  if (policy != VMP_POLICY_FIRSTFIT && policy != VMP_POLICY_BESTFIT)
-    return fail(VMP_EINVAL, "unknown policy");
+  if (const int rc = check_policy(policy)) return rc;
   if (h->rec_on) {  // recorded: one step per launch, the recorder after each
     for (int32_t k = 0; k < k_steps; k++) {
       int rc = heuristic_step_impl(h, policy, nullptr, nullptr,
@@ -801,31 +489,14 @@ int vmp_rollout_heuristic(vmp_handle *h, int32_t policy, int32_t k_steps, double
   return VMP_OK;
 }
 
-static int record_after(vmp_handle *h, const int32_t *act, const uint8_t *valid,
-                        const double *reward) {
-  RecArgs r = h->rec;
-  r.act = act;
-  r.valid = valid;
-  r.reward = reward;
-  const size_t lds = (size_t)4 * ((h->P + 63) / 64) * sizeof(unsigned long long);
-  hipLaunchKernelGGL(k_record, dim3((h->N + 3) / 4), dim3(256), lds, h->stream, h->prm, r);
-  HIP_TRY(hipGetLastError());
-  return VMP_OK;
-}
-
 int vmp_record_enable(vmp_handle *h, int32_t on) {
   if (!h) return fail(VMP_EINVAL, "null handle");
   if (!on) {
     if (h->rec_on) (void)hipStreamSynchronize(h->stream);
-    dev_free(h->rec.prev);
-    dev_free(h->rec.life_n);
-    dev_free(h->rec.alloc);
-    dev_free(h->rec.waits);
-    dev_free(h->rec.hist);
-    dev_free(h->rec.sums);
-    dev_free(h->rec_act);
-    dev_free(h->rec_valid);
-    dev_free(h->rec_reward);
+    for (void *q : {(void *)h->rec.prev, (void *)h->rec.life_n, (void *)h->rec.alloc, (void *)h->rec.waits,
+                    (void *)h->rec.hist, (void *)h->rec.sums, (void *)h->rec_act, (void *)h->rec_valid,
+                    (void *)h->rec_reward})
+      dev_free(q);
     std::memset(&h->rec, 0, sizeof(h->rec));
     h->rec_act = nullptr;
     h->rec_valid = nullptr;
@@ -873,8 +544,7 @@ int vmp_record_read(vmp_handle *h, uint32_t *hist, double *sums) {
                          hipMemcpyDeviceToDevice, h->stream));
   hipLaunchKernelGGL(k_record_close, dim3((h->N + 3) / 4), dim3(256), 0, h->stream, h->prm,
                      h->rec, hist, sums);
-  HIP_TRY(hipGetLastError());
-  return VMP_OK;
+  return launched();
 }
 
 int vmp_mask(vmp_handle *h, uint32_t *bits) {
@@ -894,8 +564,7 @@ int vmp_mask_bool(vmp_handle *h, uint8_t *mask) {
   int64_t n = rows * h->A;
   hipLaunchKernelGGL(k_mask_bool, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream,
                      rows, h->A, h->W32, h->scratch_bits, mask);
-  HIP_TRY(hipGetLastError());
-  return VMP_OK;
+  return launched();
 }
 
 int vmp_get_obs(vmp_handle *h, float *obs) {
@@ -909,31 +578,22 @@ int vmp_get_counters(vmp_handle *h, int64_t *counters) {
   if (!h || !counters) return fail(VMP_EINVAL, "null argument");
   hipLaunchKernelGGL(k_counters, dim3((h->N + 255) / 256), dim3(256), 0, h->stream, h->prm,
                      counters, nullptr);
-  HIP_TRY(hipGetLastError());
-  return VMP_OK;
+  return launched();
 }
 
 int vmp_get_stats(vmp_handle *h, double *stats) {
   if (!h || !stats) return fail(VMP_EINVAL, "null argument");
   if (h->V > kMaxVPT * kWaveSize) {
-    // beyond the static per-wave buffers: a private carve laid out from 0 for
-    // this kernel alone (ccomp | mcomp of V bytes each, then the pairwise-sum
-    // plan); the env's own carve (carve_big) places ccomp after regions this
-    // kernel does not allocate and caps it below V
+    // beyond the static per-wave buffers: a private carve for this kernel alone
     EnvParams q = h->prm;
-    q.off_ccomp = 0;
-    q.ccomp_cap = h->V;
-    q.off_leaf = (int32_t)align16(2 * (int64_t)h->V);
-    q.off_leafval = (int32_t)(q.off_leaf + align16(8 * (int64_t)q.n_leaf + 4 * 192));
-    const size_t lds = (size_t)q.off_leafval + 8 * (2 * (size_t)q.n_leaf + 64);
+    const size_t lds = carve_target_means(q);
     hipLaunchKernelGGL(k_target_means_lds, dim3(h->N), dim3(64), lds, h->stream, q);
   } else
     hipLaunchKernelGGL(k_target_means, dim3((h->N + kWavesPerBlock - 1) / kWavesPerBlock),
                        dim3(64 * kWavesPerBlock), 0, h->stream, h->prm);
   hipLaunchKernelGGL(k_counters, dim3((h->N + 255) / 256), dim3(256), 0, h->stream, h->prm,
                      nullptr, stats);
-  HIP_TRY(hipGetLastError());
-  return VMP_OK;
+  return launched();
 }
 
 int vmp_get_state(vmp_handle *h, int64_t *placement, double *vm_cpu, double *vm_mem,
@@ -942,16 +602,14 @@ int vmp_get_state(vmp_handle *h, int64_t *placement, double *vm_cpu, double *vm_
   int64_t n = (int64_t)h->N * (h->V > h->P ? h->V : h->P);
   hipLaunchKernelGGL(k_export, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream,
                      h->prm, placement, vm_cpu, vm_mem, cpu, mem, remaining, nullptr);
-  HIP_TRY(hipGetLastError());
-  return VMP_OK;
+  return launched();
 }
 
 int vmp_get_rank(vmp_handle *h, int64_t *rank) {
   if (!h || !rank) return fail(VMP_EINVAL, "null argument");
   hipLaunchKernelGGL(k_rank, dim3(h->N), dim3(64), sizeof(uint64_t) * ((h->P + 63) / 64),
                      h->stream, h->prm, rank);
-  HIP_TRY(hipGetLastError());
-  return VMP_OK;
+  return launched();
 }
 
 // ---- checkpoint / resume of the batched env state ----
@@ -970,10 +628,15 @@ struct SnapDesc {
   int32_t workload;  // 1: the handle had a per-env workload, f64 [N][2] follows the VM words
 };
 static_assert(sizeof(SnapDesc) <= kSnapHead, "snapshot descriptor exceeds its header");
-int64_t snap_bytes(const vmp_handle *h) {
-  return kSnapHead + (int64_t)sizeof(EnvHdr) * h->N + 16 * (int64_t)h->N * h->P +
-         4 * (int64_t)h->N * vm_pitch(h->V) + (h->wl ? 16 * (int64_t)h->N : 0);
-}
+// byte offsets of the parts behind the descriptor, and their sizes
+struct SnapLayout {
+  size_t nh, np, nv, nw;  // hdr, pm, vmw, workload (0 without one)
+  size_t hdr, pm, vmw, wl, end;
+  explicit SnapLayout(const vmp_handle *h)
+      : nh(sizeof(EnvHdr) * (size_t)h->N), np(16 * (size_t)h->N * h->P),
+        nv(4 * (size_t)h->N * vm_pitch(h->V)), nw(h->wl ? 16 * (size_t)h->N : 0),
+        hdr(kSnapHead), pm(hdr + nh), vmw(pm + np), wl(vmw + nv), end(wl + nw) {}
+};
 bool same_config(const vmp_config &a, const vmp_config &b) {
   vmp_config x = a, y = b;
   x.seed = y.seed = 0;
@@ -983,7 +646,7 @@ bool same_config(const vmp_config &a, const vmp_config &b) {
 
 int vmp_snapshot_bytes(const vmp_handle *h, int64_t *bytes) {
   if (!h || !bytes) return fail(VMP_EINVAL, "null argument");
-  *bytes = snap_bytes(h);
+  *bytes = (int64_t)SnapLayout(h).end;
   return VMP_OK;
 }
 
@@ -1002,15 +665,12 @@ int vmp_snapshot(vmp_handle *h, void *dst) {
   d.workload = h->wl ? 1 : 0;
   std::memcpy(head, &d, sizeof(d));
   uint8_t *o = (uint8_t *)dst;
-  const size_t nh = sizeof(EnvHdr) * (size_t)h->N, np = 16 * (size_t)h->N * h->P;
+  const SnapLayout s(h);
   HIP_TRY(hipMemcpyAsync(o, head, kSnapHead, hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(hipMemcpyAsync(o + kSnapHead, h->hdr, nh, hipMemcpyDeviceToDevice, h->stream));
-  HIP_TRY(hipMemcpyAsync(o + kSnapHead + nh, h->pm, np, hipMemcpyDeviceToDevice, h->stream));
-  const size_t nv = 4 * (size_t)h->N * vm_pitch(h->V);
-  HIP_TRY(hipMemcpyAsync(o + kSnapHead + nh + np, h->vmw, nv, hipMemcpyDeviceToDevice, h->stream));
-  if (h->wl)
-    HIP_TRY(hipMemcpyAsync(o + kSnapHead + nh + np + nv, h->wl, 16 * (size_t)h->N,
-                           hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(hipMemcpyAsync(o + s.hdr, h->hdr, s.nh, hipMemcpyDeviceToDevice, h->stream));
+  HIP_TRY(hipMemcpyAsync(o + s.pm, h->pm, s.np, hipMemcpyDeviceToDevice, h->stream));
+  HIP_TRY(hipMemcpyAsync(o + s.vmw, h->vmw, s.nv, hipMemcpyDeviceToDevice, h->stream));
+  if (h->wl) HIP_TRY(hipMemcpyAsync(o + s.wl, h->wl, s.nw, hipMemcpyHostToDevice, h->stream));
   // the descriptor's host copy is a stack buffer: the call returns after it is read
   HIP_TRY(hipStreamSynchronize(h->stream));
   return VMP_OK;
@@ -1027,21 +687,19 @@ int vmp_restore(vmp_handle *h, const void *src) {
   if (d.N != h->N || d.P != h->P || d.V != h->V || d.A != h->A || !same_config(d.cfg, h->cfg))
     return fail(VMP_EINVAL, "vmp_restore: snapshot of another env count or config");
   const uint8_t *s = (const uint8_t *)src;
-  const size_t nh = sizeof(EnvHdr) * (size_t)h->N, np = 16 * (size_t)h->N * h->P;
+  const SnapLayout l(h);
   // the env state continues bit-exactly only under the workload it ran with
   if ((d.workload != 0) != (h->wl != nullptr))
     return fail(VMP_EINVAL, "vmp_restore: snapshot and handle differ in having a per-env workload");
   if (h->wl) {
     std::vector<double> w(2 * (size_t)h->N);
-    HIP_TRY(hipMemcpy(w.data(), s + kSnapHead + nh + np + 4 * (size_t)h->N * vm_pitch(h->V),
-                      16 * (size_t)h->N, hipMemcpyDeviceToHost));
-    if (std::memcmp(w.data(), h->wl, 16 * (size_t)h->N) != 0)
+    HIP_TRY(hipMemcpy(w.data(), s + l.wl, l.nw, hipMemcpyDeviceToHost));
+    if (std::memcmp(w.data(), h->wl, l.nw) != 0)
       return fail(VMP_EINVAL, "vmp_restore: snapshot of another per-env workload");
   }
-  HIP_TRY(hipMemcpyAsync(h->hdr, s + kSnapHead, nh, hipMemcpyDeviceToDevice, h->stream));
-  HIP_TRY(hipMemcpyAsync(h->pm, s + kSnapHead + nh, np, hipMemcpyDeviceToDevice, h->stream));
-  HIP_TRY(hipMemcpyAsync(h->vmw, s + kSnapHead + nh + np, 4 * (size_t)h->N * vm_pitch(h->V),
-                         hipMemcpyDeviceToDevice, h->stream));
+  HIP_TRY(hipMemcpyAsync(h->hdr, s + l.hdr, l.nh, hipMemcpyDeviceToDevice, h->stream));
+  HIP_TRY(hipMemcpyAsync(h->pm, s + l.pm, l.np, hipMemcpyDeviceToDevice, h->stream));
+  HIP_TRY(hipMemcpyAsync(h->vmw, s + l.vmw, l.nv, hipMemcpyDeviceToDevice, h->stream));
   return VMP_OK;
 }
 
@@ -1065,9 +723,8 @@ int vmp_debug_fail_alloc(int32_t n) {
 int vmp_debug_occupancy(vmp_handle *h, int32_t *blocks_per_cu, int32_t *lds_bytes) {
   if (!h || !blocks_per_cu || !lds_bytes) return fail(VMP_EINVAL, "null argument");
   if (!h->big) return fail(VMP_EINVAL, "occupancy query covers the block kernel (V > 1024) only");
-  int spt, nt;
-  big_shape(h->V, spt, nt);
-  const size_t lds1 = (size_t)align16(h->prm.off_pre + 20 * (int64_t)kSpecDraws + 4) + 4 * (size_t)spt * nt;
+  const int spt = big_spt(h->V);
+  const size_t lds1 = launch_lds(h->prm, 1, true, spt);  // the per-step launch
   int st = 0;
   *blocks_per_cu = big_occupancy(spt, lds1, &st);
   *lds_bytes = (int32_t)lds1 + st;

@@ -35,15 +35,10 @@ namespace vmp {
 // one row per iteration costs one LDS round trip per row).
 #define VMP_SLOOP _Pragma("unroll 4")
 
-// k_env_big's workgroup: 6 waves (two workgroups per CU at 3 waves/SIMD); a
-// compile-time thread count so slot s of a thread sits at a constant LDS
-// offset s * kBigNT * 4 (immediate ds offsets, no per-slot address registers).
-// Up to kBigMaxSPT slots per thread (V <= kBigNT * kBigMaxSPT).
-constexpr int kBigNT = 256;
-// per-thread slot sets (bit s: slot s * kBigNT + t)
+// per-thread slot sets (bit s: slot s * kBigNT + t; kBigNT, kBigMaxSPT: vmp_carve.h)
 typedef uint64_t SMask;
 #define SBIT(s) ((SMask)1 << (s))
-constexpr int kBigMaxSPT = (10240 + kBigNT - 1) / kBigNT, kBigMaxWaves = kBigNT / 64;
+constexpr int kBigMaxWaves = kBigNT / 64;
 static_assert(kBigNT % 64 == 0 && kBigNT <= 512 && kBigMaxSPT <= 64, "block shape");
 // k_env_big's per-step helpers (pairwise-sum jobs, reward, draws): inlined
 // (round 3: out of line, every call saved and restored the caller's live
@@ -914,19 +909,19 @@ __device__ __forceinline__ double big_tail(const EnvParams &p, const Lds &L, con
   // actions keep the full clamp pass below
   const bool clamp_inline = heur;
 #pragma unroll 1
-  for (int j0 = 0; j0 < n_term; j0 += 512) {
+  for (int j0 = 0; j0 < n_term; j0 += kEvCap) {
     if (ballot(fterm != 0)) {  // waves without finishers skip the ranking
       int rb;
       const int pre = row_prefix<SPT>(B, rb);
 VMP_SLOOP
       for (int s = 0; s < SPT; s++) {
         const int r = __builtin_amdgcn_readlane(pre, s) + below(ballot((fterm >> s) & 1u), lane);
-        if (((fterm >> s) & 1u) && r >= j0 && r < j0 + 512) L.evw[r - j0] = wr[s];
+        if (((fterm >> s) & 1u) && r >= j0 && r < j0 + kEvCap) L.evw[r - j0] = wr[s];
       }
     }
     __syncthreads();
     if (w0) {
-      const int nt = n_term - j0 < 512 ? n_term - j0 : 512;
+      const int nt = n_term - j0 < kEvCap ? n_term - j0 : kEvCap;
 #pragma unroll 1
       for (int i = 0; i < nt; i++) {  // frees in ascending VM order
         const uint32_t ew = L.evw[i];
@@ -975,8 +970,8 @@ VMP_SLOOP
   if (k > 0) {
     Pcg r1 = ld_pcg(H, 0), r2 = ld_pcg(H, 1);
 #pragma unroll 1
-    for (int64_t j0 = 0; j0 < k; j0 += 512) {
-      const int64_t j1 = j0 + 512 < k ? j0 + 512 : k;
+    for (int64_t j0 = 0; j0 < k; j0 += kEvCap) {
+      const int64_t j1 = j0 + kEvCap < k ? j0 + kEvCap : k;
       if (w0) {
 #pragma unroll 1
         for (int64_t j = j0; j < j1; j++) {

@@ -21,14 +21,14 @@
 namespace vmp {
 
 // --------------------------------------------------------- env kernel ----
-// Per-wave LDS carve (offsets from EnvParams, computed by the host).
+// Per-wave LDS carve (offsets from EnvParams, computed by the host: vmp_carve.h).
 struct Lds {
   EnvHdr LDSP *hdr;                  // the env's 256-B header (scalars, RNG streams)
   double LDSP *cpu, *mem;       // f64[P] PM resources (the env state)
   float LDSP *fcpu, *fmem;      // f32[P] observation view used by the heuristics
   uint8_t LDSP *tc, *tm;        // per-PM largest fitting size (hundredths), f32 semantics
   uint16_t LDSP *ord;                // BF ascending argsort, then reversed into visiting order
-  uint64_t LDSP *bc, *bm;       // action phase: the any-fit table (u32 [128] at bc)
+  uint64_t LDSP *bc;                 // action phase: the any-fit table (u32 [128] at bc)
   int32_t LDSP *sortstk;             // introsort stacks
   uint16_t LDSP *nulls;              // NULL slot indices (aliases the fit bitmaps)
   uint8_t LDSP *accc, *accm;    // accepted sizes (alias the fit bitmaps)
@@ -40,7 +40,7 @@ struct Lds {
   int32_t LDSP *svcinfo;             // [0] speculative count, [1] consumed
   uint8_t LDSP *ccomp, *mcomp;  // compressed sizes of existing VMs [ccomp_cap]
   uint64_t LDSP *pdirty;             // bit i: PM double i (cpu | memory) changed
-  uint32_t LDSP *evw;                // k_env_big event lists [512]: VM word,
+  uint32_t LDSP *evw;                // k_env_big event lists [kEvCap]: VM word,
   int32_t LDSP *evt;                 //   target / value,
   uint8_t LDSP *evok;                //   result
   PwLds pw;
@@ -60,23 +60,22 @@ __device__ __forceinline__ Lds make_lds(const EnvParams &p, char LDSP *base) {
   L.tm = L.tc + p.tm_off;
   L.ord = reinterpret_cast<uint16_t LDSP *>(base + p.off_ord);
   L.bc = reinterpret_cast<uint64_t LDSP *>(base + p.off_bits);
-  L.bm = L.bc + 101 * p.NW;
   L.sortstk = reinterpret_cast<int32_t LDSP *>(base + p.off_sort);
   L.nulls = reinterpret_cast<uint16_t LDSP *>(base + p.off_bits);
   L.accc = reinterpret_cast<uint8_t LDSP *>(base + p.off_acc);
   L.accm = L.accc + p.acc_cap;
   L.jobres = reinterpret_cast<double LDSP *>(base + p.off_stage);
-  L.svcinfo = reinterpret_cast<int32_t LDSP *>(base + p.off_stage + 8 * 12);
-  L.svcfb = reinterpret_cast<uint64_t LDSP *>(base + p.off_stage + 8 * 14);
+  L.svcinfo = reinterpret_cast<int32_t LDSP *>(base + p.off_stage + kStageSvcInfo);
+  L.svcfb = reinterpret_cast<uint64_t LDSP *>(base + p.off_stage + kStageSvcFb);
   L.svcst = reinterpret_cast<uint64_t LDSP *>(base + p.off_pre);
-  L.svc = reinterpret_cast<uint32_t LDSP *>(base + p.off_pre + 16 * p.scap);
-  L.arr = reinterpret_cast<int32_t LDSP *>(base + p.off_pre + 20 * p.scap);
+  L.svc = reinterpret_cast<uint32_t LDSP *>(base + p.off_pre + kSpecStateBytes * p.scap);
+  L.arr = reinterpret_cast<int32_t LDSP *>(base + p.off_pre + kSpecDrawBytes * p.scap);
   L.pdirty = reinterpret_cast<uint64_t LDSP *>(base + p.off_pdirty);
   L.ccomp = reinterpret_cast<uint8_t LDSP *>(base + p.off_ccomp);
   L.mcomp = L.ccomp + p.ccomp_cap;
   L.evw = reinterpret_cast<uint32_t LDSP *>(base + p.off_ev);
-  L.evt = reinterpret_cast<int32_t LDSP *>(L.evw + 512);
-  L.evok = reinterpret_cast<uint8_t LDSP *>(L.evt + 512);
+  L.evt = reinterpret_cast<int32_t LDSP *>(L.evw + kEvCap);
+  L.evok = reinterpret_cast<uint8_t LDSP *>(L.evt + kEvCap);
   L.pw.lo = reinterpret_cast<int32_t LDSP *>(base + p.off_leaf);
   L.pw.len = L.pw.lo + p.n_leaf;
   L.pw.stk = L.pw.len + p.n_leaf;
@@ -281,7 +280,7 @@ __device__ __forceinline__ int bf_tie(const EnvParams &p, const Lds &L, int kc, 
   const uint8_t LDSP *tc = L.tc, *tm = L.tm;
   const int pos = wave_aqselect_top(
       KeySum{L.fcpu, L.fmem}, L.ord, P, L.sortstk, lo, hi,
-      reinterpret_cast<uint16_t LDSP *>(L.sortstk + 256),
+      reinterpret_cast<uint16_t LDSP *>(L.sortstk + kSortStackWords),
       [=](int q) { return (int)tc[q] - 1 >= kc && (int)tm[q] - 1 >= km; });
   return pos >= 0 ? (int)L.ord[pos] : -1;  // visiting order: descending positions
 }

@@ -48,11 +48,7 @@ int64_t quiet_violations_take() {
 #endif
 }
 
-// host side: the block kernel's geometry and launcher (vmp_capi.cpp)
-void big_geometry(int *nt, int *spt_max) {
-  *nt = kBigNT;
-  *spt_max = kBigMaxSPT;
-}
+// host side: the block kernel's launcher (vmp_capi.cpp)
 void launch_big_env(int spt, bool one, int n_env, size_t lds, hipStream_t s, const EnvParams &p,
                     const StepOut &o) {
   if (one) launch_big_one<true, false>(spt, n_env, lds, s, p, o);

@@ -28,6 +28,7 @@
 // vm_suspended / vm_planned_runtime are never read on the path (SURVEY App. B
 // item 14) and are not stored.
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 
 namespace vmp {
@@ -107,9 +108,9 @@ struct EnvParams {
   uint32_t *vmw;          // [N][vm_pitch(V)] (slot words | time words per 64-slot block)
   double *pm;
   EnvHdr *hdr;
-  // per-wave LDS carve (bytes); offsets inside one wave's region
+  // per-wave LDS carve (bytes; vmp_carve.h); offsets inside one wave's region
   int32_t lds_wave_bytes;
-  int32_t NW;      // ceil(P/64) words per fit bitmap row
+  int32_t NW;      // reserved: ceil(P/64), still written; no kernel reads it
   int32_t n_leaf;  // capacity of the pairwise-sum leaf list
   int32_t off_hdr, off_pm, off_fpm, off_thr, off_ord, off_bits, off_sort, off_ccomp;
   int32_t off_leaf, off_leafval, off_stage, off_pre;
@@ -127,6 +128,10 @@ struct EnvParams {
   // whose accepted (> acc_cap) or existing (> ccomp_cap) VMs exceed the LDS copy
   uint8_t *bigscr;
 };
+static_assert(sizeof(EnvParams) == 232 && offsetof(EnvParams, pois) == 80 &&
+                  offsetof(EnvParams, lds_wave_bytes) == 120 && offsetof(EnvParams, off_pre) == 176 &&
+                  offsetof(EnvParams, jump) == 216 && offsetof(EnvParams, bigscr) == 224,
+              "EnvParams is the kernarg of every kernel: its layout stays");
 
 struct StepOut {
   const int32_t *actions;  // external actions [N][V] or null (heuristic)

@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "vmp_carve.h"
 #include "vmp_dev.h"
 
 namespace vmp {
@@ -190,9 +191,9 @@ __device__ __forceinline__ double wave_pw_sum(int n, F f, const PwLds &S) {
   }
   // deeper recursion (n > pw_reg_cap(RD), P-sized sums of big configs): LDS plan
   int nl = 1;
-  if (lane == 0) S.stk[191] = pw_plan(n, S);
+  if (lane == 0) S.stk[kPwStackWords - 1] = pw_plan(n, S);
   wsync();
-  nl = S.stk[191];
+  nl = S.stk[kPwStackWords - 1];
   for (int b = 0; b < nl; b += 8) {
     const int l = b + (lane >> 3);
     const int o = l < nl ? S.lo[l] : 0, m = l < nl ? S.len[l] : 0;
