@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define VMP_ABI_VERSION 12
+#define VMP_ABI_VERSION 13
 
 #define VMP_OK 0
 #define VMP_EINVAL (-1)
@@ -151,6 +151,51 @@ int vmp_dims(const vmp_handle *h, int32_t *n_env, int32_t *P, int32_t *V, int32_
 int vmp_set_workload(vmp_handle *h, const double *arrival_rate, const double *service_length);
 /* Current per-env values (the config's for a handle never given a workload); HOST arrays, nullable. */
 int vmp_get_workload(const vmp_handle *h, double *arrival_rate, double *service_length);
+
+/* Trace-driven workload: envs replay the caller's requests instead of drawing them.
+ * A trace is `steps` steps of requests: offs int64[steps + 1] (offs[0] = 0, non-decreasing,
+ * offs[steps] < 2^31) and per request cpu, mem (hundredths, 1..100) and runtime (1..2^30).
+ * The requests of step index s are [offs[s], offs[s+1]), in order. On a traced env the step
+ * run at timestep s + 1 (reset leaves timestep 1) runs _accept_vm_requests (env.py:271-293)
+ * with a = offs[s+1] - offs[s] arrivals (0 from step `steps` on): the k = min(a, #NULL) lowest
+ * NULL slots take the step's first k requests in order (vm_cpu = cpu/100, vm_mem = mem/100,
+ * planned = remaining = runtime), total_requests += a, dropped += a - k. A DROPPED REQUEST IS
+ * CONSUMED: it is never offered again and the next step starts at offs[s+1]. (The draw-based
+ * env draws sizes and runtimes per accepted VM, so there a drop consumes no draw; this is the
+ * one deliberate difference, and what makes the request sequence independent of the policy.)
+ * RNG streams 1-4 are neither read nor advanced; everything else of the step is unchanged.
+ * vmp_reset rewinds an env to step 0 of its trace (its seeds still reseed the idle streams).
+ *
+ * vmp_set_trace: HOST arrays, copied by the call. trace_of_env int32[n_env] maps each env to
+ * a trace (NULL: every env replays trace 0). Null pointers, offs[0] != 0, a decreasing offs,
+ * a size of 0 or above 100, a runtime of 0 or above 2^30 and a map entry out of range return
+ * VMP_EINVAL, a failed device allocation VMP_EOOM; both leave the handle exactly as it was,
+ * usable with its previous trace or its RNG workload. Stream-ordered behind the launches
+ * already queued; synchronises the stream, so it must not be made during capture. A handle
+ * with a per-env workload may be given a trace: the workload is dormant until
+ * vmp_clear_trace. On a traced handle vmp_set_workload returns VMP_ESTATE.
+ * Graphs: the first vmp_set_trace (and vmp_clear_trace) switches the handle's step kernels,
+ * so graphs captured before it must be recaptured. Later calls rewrite the device-side
+ * descriptor table in place: a graph captured on a traced handle stays valid across them and
+ * replays the new traces.
+ * Snapshots of a traced handle carry a flag and a 64-bit hash of (traces, map); vmp_restore
+ * needs the same hash on the target and refuses traced into plain and the reverse
+ * (VMP_EINVAL). The snapshot size does not change. (ABI 13) */
+typedef struct vmp_trace {
+  int64_t steps;
+  const int64_t *offs;     /* [steps + 1] */
+  const uint8_t *cpu;      /* [offs[steps]] */
+  const uint8_t *mem;      /* [offs[steps]] */
+  const uint32_t *runtime; /* [offs[steps]] */
+} vmp_trace;
+int vmp_set_trace(vmp_handle *h, int32_t n_traces, const vmp_trace *traces,
+                  const int32_t *trace_of_env);
+/* Back to the RNG workload (per-env if the handle had one), the streams where they stood. */
+int vmp_clear_trace(vmp_handle *h);
+/* n_traces (0: no trace); then, all HOST and nullable: trace_of_env int32[n_env],
+ * steps / requests int64[n_traces] of every trace. */
+int vmp_trace_info(const vmp_handle *h, int32_t *n_traces, int32_t *trace_of_env, int64_t *steps,
+                   int64_t *requests);
 
 /* VmEnv.reset (env.py:180-226) for the envs whose env_mask byte is non-zero
  * (env_mask may be NULL = all). seeds: device int64[n_env] or NULL; a NULL

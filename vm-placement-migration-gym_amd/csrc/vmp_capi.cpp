@@ -15,6 +15,7 @@
 #include "vmp_kernels.h"
 #include "vmp_layout.h"
 #include "vmp_record.h"
+#include "vmp_trace.h"
 
 using namespace vmp;
 
@@ -54,6 +55,15 @@ struct vmp_handle {
                         // non-null selects the WL = true kernels (launch_env)
   double *lg_shared;    // device loggam table shared by all PTRS records of pois_env
   int32_t lg_shared_n;
+  // trace-driven workload (vmp_set_trace); all null / 0 without one
+  TraceDesc *tr_tab;    // device [N], prm.pois while set (address stable until vmp_clear_trace);
+                        // non-null selects the trace kernels (launch_env)
+  uint64_t *tr_data;    // device: every trace's offs and packed requests (vmp_trace.h)
+  TraceDesc *tr_host;   // host mirror of tr_tab
+  int32_t tr_n;         // traces
+  int32_t *tr_map;      // host [N]
+  int64_t *tr_info;     // host [tr_n][2]: steps, requests
+  uint64_t tr_hash;     // content hash of (traces, map), carried by snapshots
 };
 
 namespace {
@@ -63,7 +73,13 @@ namespace {
 // (p.pois is [N][2]: the kernels of vmp_kernels_wl.hip)
 using EnvKernel = void (*)(EnvParams, StepOut);
 template <int VPT>
-EnvKernel env_kernel(bool ext, bool one, bool wl) {
+EnvKernel env_kernel_tr(bool ext, bool one) {  // the handle has a trace: vmp_kernels_tr.hip
+  if (ext) return k_env_ext_tr<VPT>;
+  return one ? k_env_tr<VPT, true> : k_env_tr<VPT, false>;
+}
+template <int VPT>
+EnvKernel env_kernel(bool ext, bool one, bool wl, bool tr) {
+  if (tr) return env_kernel_tr<VPT>(ext, one);
   if (ext) return wl ? k_env_ext<VPT, true> : k_env_ext<VPT, false>;
   if (one) return wl ? k_env<VPT, true, true> : k_env<VPT, true, false>;
   return wl ? k_env<VPT, false, true> : k_env<VPT, false, false>;
@@ -72,14 +88,15 @@ EnvKernel env_kernel(bool ext, bool one, bool wl) {
 int launch_env(vmp_handle *h, const StepOut &o) {
   dim3 grid((h->N + kEnvWavesPerBlock - 1) / kEnvWavesPerBlock), block(64 * kEnvWavesPerBlock);
   EnvParams p = h->prm;
-  const bool wl = h->pois_env != nullptr;
+  const bool wl = h->pois_env != nullptr, tr = h->tr_tab != nullptr;
   const int spt = big_spt(h->V);
   p.scap = kSpecDraws;
   p.lds_wave_bytes = launch_wave_bytes(p, o.k_steps);
   const size_t lds = launch_lds(p, o.k_steps, h->big, spt);
   if (!lds_fits(lds, h->big)) return fail(VMP_EINVAL, "config too large for the LDS carve");
   if (h->big) {  // one workgroup per env
-    if (wl) launch_big_env_wl(spt, o.k_steps == 1, h->N, lds, h->stream, p, o);
+    if (tr) launch_big_env_tr(spt, o.k_steps == 1, h->N, lds, h->stream, p, o);
+    else if (wl) launch_big_env_wl(spt, o.k_steps == 1, h->N, lds, h->stream, p, o);
     else launch_big_env(spt, o.k_steps == 1, h->N, lds, h->stream, p, o);
     return launched();
   }
@@ -88,7 +105,7 @@ int launch_env(vmp_handle *h, const StepOut &o) {
   const int need = (h->V + 63) / 64;  // the fewest of 1 / 2 / 4 / 8 / 16 rows that hold V
   const auto pick = need <= 1 ? env_kernel<1> : need <= 2 ? env_kernel<2> : need <= 4 ? env_kernel<4>
                     : need <= 8 ? env_kernel<8> : env_kernel<16>;
-  hipLaunchKernelGGL(pick(o.actions != nullptr, o.k_steps == 1, wl), grid, block, lds, h->stream, p, o);
+  hipLaunchKernelGGL(pick(o.actions != nullptr, o.k_steps == 1, wl, tr), grid, block, lds, h->stream, p, o);
   return launched();
 }
 
@@ -241,10 +258,14 @@ int vmp_destroy(vmp_handle *h) {
   if (!h) return VMP_OK;
   for (void *q : {(void *)h->vmw, (void *)h->pm, (void *)h->hdr, (void *)h->lg_arr, (void *)h->lg_svc,
                   (void *)h->scratch_bits, (void *)h->pois_dev, (void *)h->jump_dev, (void *)h->bigscr,
-                  (void *)h->stamps, (void *)h->pois_env, (void *)h->lg_shared})
+                  (void *)h->stamps, (void *)h->pois_env, (void *)h->lg_shared, (void *)h->tr_tab,
+                  (void *)h->tr_data})
     dev_free(q);
   std::free(h->wl);
   std::free(h->wl_rec);
+  std::free(h->tr_host);
+  std::free(h->tr_map);
+  std::free(h->tr_info);
   vmp_record_enable(h, 0);
   delete h;
   return VMP_OK;
@@ -258,6 +279,7 @@ int vmp_destroy(vmp_handle *h) {
 // table / loggam_far branch exactly where a homogeneous handle of its rate does.
 int vmp_set_workload(vmp_handle *h, const double *arrival_rate, const double *service_length) {
   if (!h) return fail(VMP_EINVAL, "null handle");
+  if (h->tr_tab) return fail(VMP_ESTATE, "vmp_set_workload: the handle has a trace (vmp_clear_trace first)");
   if (!arrival_rate && !service_length) return VMP_OK;
   const size_t N = (size_t)h->N;
   for (size_t i = 0; i < N; i++) {
@@ -350,6 +372,127 @@ int vmp_get_workload(const vmp_handle *h, double *arrival_rate, double *service_
   for (int32_t i = 0; i < h->N; i++) {
     if (arrival_rate) arrival_rate[i] = h->wl ? h->wl[2 * i] : h->cfg.arrival_rate;
     if (service_length) service_length[i] = h->wl ? h->wl[2 * i + 1] : h->cfg.service_length;
+  }
+  return VMP_OK;
+}
+
+// ---- trace-driven workload ----
+// One device block holds every trace (offs, then packed requests: vmp_trace.h);
+// the per-env descriptor table points into it. The first call allocates the
+// table and moves prm.pois to it (launch_env then picks the trace kernels);
+// later calls rewrite it in place behind the queued launches.
+int vmp_set_trace(vmp_handle *h, int32_t n_traces, const vmp_trace *traces,
+                  const int32_t *trace_of_env) {
+  if (!h) return fail(VMP_EINVAL, "null handle");
+  if (const char *why = trace_check(n_traces, traces, trace_of_env, h->N)) return fail(VMP_EINVAL, why);
+  const size_t N = (size_t)h->N;
+  std::vector<size_t> at((size_t)n_traces);
+  size_t words = 0;
+  for (int32_t i = 0; i < n_traces; i++) {
+    at[(size_t)i] = words;
+    words += trace_words(traces[i]);
+  }
+  std::vector<uint64_t> data(words);
+  for (int32_t i = 0; i < n_traces; i++) trace_pack(traces[i], data.data() + at[(size_t)i]);
+  // host copies first: nothing below them can fail halfway
+  TraceDesc *host_new = (TraceDesc *)std::malloc(sizeof(TraceDesc) * N);
+  int32_t *map_new = (int32_t *)std::malloc(sizeof(int32_t) * N);
+  int64_t *info_new = (int64_t *)std::malloc(sizeof(int64_t) * 2 * (size_t)n_traces);
+  uint64_t *data_new = nullptr;
+  TraceDesc *tab_new = nullptr;
+  const bool first = h->tr_tab == nullptr;
+  int rc = VMP_OK;
+  if (!host_new || !map_new || !info_new) rc = fail(VMP_EOOM, "vmp_set_trace: host allocation failed");
+  if (rc == VMP_OK) {
+    hipError_t e = dev_malloc(&data_new, sizeof(uint64_t) * words);
+    if (e == hipSuccess && first) e = dev_malloc(&tab_new, sizeof(TraceDesc) * N);
+    if (e != hipSuccess)
+      rc = fail(e == hipErrorOutOfMemory ? VMP_EOOM : VMP_EDEVICE,
+                std::string("vmp_set_trace: ") + hipGetErrorString(e));
+  }
+  if (rc == VMP_OK) {
+    for (size_t e = 0; e < N; e++) {
+      const int32_t i = trace_of_env ? trace_of_env[e] : 0;
+      const uint64_t *base = data_new + at[(size_t)i];
+      map_new[e] = i;
+      host_new[e] = TraceDesc{reinterpret_cast<const int64_t *>(base), base + traces[i].steps + 1,
+                              traces[i].steps, 0};
+    }
+    for (int32_t i = 0; i < n_traces; i++) {
+      info_new[2 * i] = traces[i].steps;
+      info_new[2 * i + 1] = traces[i].offs[traces[i].steps];
+    }
+    // stream-ordered behind the launches already queued, which read the old
+    // table and arrays; the call returns once the new ones are in place
+    TraceDesc *dst = first ? tab_new : h->tr_tab;
+    hipError_t e = hipMemcpyAsync(data_new, data.data(), sizeof(uint64_t) * words,
+                                  hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess)
+      e = hipMemcpyAsync(dst, host_new, sizeof(TraceDesc) * N, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) {
+      rc = fail(VMP_EDEVICE, std::string("vmp_set_trace copy: ") + hipGetErrorString(e));
+      if (!first) {  // put the previous table back before the new arrays go
+        (void)hipMemcpyAsync(dst, h->tr_host, sizeof(TraceDesc) * N, hipMemcpyHostToDevice, h->stream);
+        (void)hipStreamSynchronize(h->stream);
+      }
+    }
+  }
+  if (rc != VMP_OK)
+    return fail_after(rc, [&] {
+      dev_free(data_new);
+      dev_free(tab_new);
+      std::free(host_new);
+      std::free(map_new);
+      std::free(info_new);
+    });
+  // commit. No queued launch reads the old arrays any more (synchronised above)
+  dev_free(h->tr_data);
+  std::free(h->tr_host);
+  std::free(h->tr_map);
+  std::free(h->tr_info);
+  h->tr_data = data_new;
+  h->tr_host = host_new;
+  h->tr_map = map_new;
+  h->tr_info = info_new;
+  h->tr_n = n_traces;
+  h->tr_hash = trace_hash(n_traces, traces, trace_of_env, h->N);
+  if (first) {
+    h->tr_tab = tab_new;
+    h->prm.pois = reinterpret_cast<const PoisConst *>(tab_new);  // launch_env: the trace kernels
+  }
+  return VMP_OK;
+}
+
+int vmp_clear_trace(vmp_handle *h) {
+  if (!h) return fail(VMP_EINVAL, "null handle");
+  if (!h->tr_tab) return VMP_OK;
+  HIP_TRY(hipStreamSynchronize(h->stream));  // queued launches read the table
+  h->prm.pois = h->pois_env ? h->pois_env : h->pois_dev;
+  dev_free(h->tr_tab);
+  dev_free(h->tr_data);
+  std::free(h->tr_host);
+  std::free(h->tr_map);
+  std::free(h->tr_info);
+  h->tr_tab = nullptr;
+  h->tr_data = nullptr;
+  h->tr_host = nullptr;
+  h->tr_map = nullptr;
+  h->tr_info = nullptr;
+  h->tr_n = 0;
+  h->tr_hash = 0;
+  return VMP_OK;
+}
+
+int vmp_trace_info(const vmp_handle *h, int32_t *n_traces, int32_t *trace_of_env, int64_t *steps,
+                   int64_t *requests) {
+  if (!h) return fail(VMP_EINVAL, "null handle");
+  if (n_traces) *n_traces = h->tr_n;
+  if (!h->tr_tab) return VMP_OK;
+  if (trace_of_env) std::memcpy(trace_of_env, h->tr_map, sizeof(int32_t) * (size_t)h->N);
+  for (int32_t i = 0; i < h->tr_n; i++) {
+    if (steps) steps[i] = h->tr_info[2 * i];
+    if (requests) requests[i] = h->tr_info[2 * i + 1];
   }
   return VMP_OK;
 }
@@ -626,6 +769,8 @@ struct SnapDesc {
   int32_t N, P, V, A;
   vmp_config cfg;  // seed excluded from the compatibility check
   int32_t workload;  // 1: the handle had a per-env workload, f64 [N][2] follows the VM words
+  int32_t traced;    // 1: the handle had a trace (vmp_set_trace) of content hash trace_hash
+  uint64_t trace_hash;
 };
 static_assert(sizeof(SnapDesc) <= kSnapHead, "snapshot descriptor exceeds its header");
 // byte offsets of the parts behind the descriptor, and their sizes
@@ -663,6 +808,8 @@ int vmp_snapshot(vmp_handle *h, void *dst) {
   d.N = h->N, d.P = h->P, d.V = h->V, d.A = h->A;
   d.cfg = h->cfg;
   d.workload = h->wl ? 1 : 0;
+  d.traced = h->tr_tab ? 1 : 0;
+  d.trace_hash = h->tr_hash;
   std::memcpy(head, &d, sizeof(d));
   uint8_t *o = (uint8_t *)dst;
   const SnapLayout s(h);
@@ -691,6 +838,11 @@ int vmp_restore(vmp_handle *h, const void *src) {
   // the env state continues bit-exactly only under the workload it ran with
   if ((d.workload != 0) != (h->wl != nullptr))
     return fail(VMP_EINVAL, "vmp_restore: snapshot and handle differ in having a per-env workload");
+  // ... and a traced env only under the very requests it was replaying
+  if ((d.traced != 0) != (h->tr_tab != nullptr))
+    return fail(VMP_EINVAL, "vmp_restore: snapshot and handle differ in having a trace");
+  if (h->tr_tab && d.trace_hash != h->tr_hash)
+    return fail(VMP_EINVAL, "vmp_restore: snapshot of another trace");
   if (h->wl) {
     std::vector<double> w(2 * (size_t)h->N);
     HIP_TRY(hipMemcpy(w.data(), s + l.wl, l.nw, hipMemcpyDeviceToHost));

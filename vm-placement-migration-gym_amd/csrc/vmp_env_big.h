@@ -854,7 +854,7 @@ __device__ __forceinline__ void big_store_obs(const EnvParams &p, const Lds &L, 
 // each step and written back as they change (placed, suspended, finished,
 // accepted), so no per-slot time registers live across the step; the low
 // halves live in LDS (W) and are stored by big_store (`dirty`).
-template <int SPT, bool WL>
+template <int SPT, int SRC>
 __device__ __forceinline__ double big_tail(const EnvParams &p, const Lds &L, const Tables &T,
                                            BigShared &B, uint32_t LDSP *W, SMask run0,
                                            SMask &dirty, int kstep, bool &terminated,
@@ -972,12 +972,28 @@ VMP_SLOOP
 #pragma unroll 1
     for (int64_t j0 = 0; j0 < k; j0 += kEvCap) {
       const int64_t j1 = j0 + kEvCap < k ? j0 + kEvCap : k;
-      if (w0) {
+      if (SRC == kSrcTrace && w0) {
+        // a traced env: wave 0 reads the chunk's requests, one per lane
+        const uint64_t GLBP *req = gptr(env_trace(p, e).req) + L.svcfb[0];
+#pragma unroll 1
+        for (int64_t j = j0 + lane; j < j1; j += 64) {
+          const uint64_t rq = req[j];
+          if (acc_g) {
+            gsc[j] = (uint8_t)rq_cc(rq);
+            gsc[p.V + j] = (uint8_t)rq_cm(rq);
+          } else {
+            L.accc[j] = (uint8_t)rq_cc(rq);
+            L.accm[j] = (uint8_t)rq_cm(rq);
+          }
+          L.evt[j - j0] = (int32_t)rq_rt(rq);
+        }
+      }
+      if (SRC != kSrcTrace && w0) {
 #pragma unroll 1
         for (int64_t j = j0; j < j1; j++) {
           const int cc = (int)rint((p.seq_lo + p.seq_range * next_double(r1)) * 100.0);
           const int cm = (int)rint((p.seq_lo + p.seq_range * next_double(r2)) * 100.0);
-          const uint32_t rr = svc_take<WL>(p, L, e);
+          const uint32_t rr = svc_take<SRC>(p, L, e);
           if (lane == 0) {
             if (acc_g) {
               gsc[j] = (uint8_t)cc;
@@ -1006,12 +1022,14 @@ VMP_SLOOP
       }
       __syncthreads();
     }
-    if (w0) {
+    if (SRC != kSrcTrace && w0) {
       st_pcg(H, 0, r1);
       st_pcg(H, 1, r2);
     }
   }
   __syncthreads();
+  // (a traced env: every request of the step is consumed, dropped ones too)
+  if (SRC == kSrcTrace && t == 0) L.svcfb[0] += (uint64_t)arrivals;
   STAMP(15);
   // the VM words and PM resources are final: their owners store them now
   if (store_state) big_store_words<SPT>(p, L, wr, dirty, e);
@@ -1095,8 +1113,11 @@ VMP_SLOOP
 // live around the K-step loop's back edge, which spilled them around the sums.
 // (both instantiations are register-allocated for 2 waves per SIMD)
 // WL = true: the kernel of handles with a per-env workload (env_pois).
-template <int SPT, bool ONE, bool WL = false>
+// TR = true: of handles with a trace (vmp_set_trace: trace_preload, big_tail),
+// instantiated by vmp_kernels_tr.hip alone.
+template <int SPT, bool ONE, bool WL = false, bool TR = false>
 __global__ __launch_bounds__(kBigNT, 2) void k_env_big(EnvParams p, StepOut o) {
+  constexpr int SRC = TR ? kSrcTrace : WL ? kSrcEnv : kSrcConfig;
   extern __shared__ __align__(16) char lds[];
   __shared__ Tables T;
   __shared__ BigShared B;
@@ -1119,7 +1140,7 @@ __global__ __launch_bounds__(kBigNT, 2) void k_env_big(EnvParams p, StepOut o) {
     T.fcent[i] = (float)((double)i / 100.0);
   }
   constexpr int kPoisWords = (int)(2 * sizeof(PoisConst) / 4);
-  if (t < kPoisWords) reinterpret_cast<uint32_t *>(T.pois)[t] = gptr(reinterpret_cast<const uint32_t *>(env_pois<WL>(p, e)))[t];
+  if (SRC != kSrcTrace && t < kPoisWords) reinterpret_cast<uint32_t *>(T.pois)[t] = gptr(reinterpret_cast<const uint32_t *>(env_pois<SRC>(p, e)))[t];
   // every global load of the env's state is issued before the first LDS store
   // (indices clamped, not branched on, so the loads are unconditional):
   // header, the first 4*NT PM words, the VM words
@@ -1137,7 +1158,8 @@ __global__ __launch_bounds__(kBigNT, 2) void k_env_big(EnvParams p, StepOut o) {
     // other waves load the VM words (the two never hold registers at once)
     if (o.k_steps > 0) {
       wsync();
-      big_predraw(p, T, L.base, o.k_steps, p.jump + 4 * lane);
+      if constexpr (SRC == kSrcTrace) trace_preload(make_lds(p, L.base), env_trace(p, e), o.k_steps);
+      else big_predraw(p, T, L.base, o.k_steps, p.jump + 4 * lane);
     }
   } else {
     // waves 1.. load the low halves of all VM words (placement, sizes) into W;
@@ -1186,7 +1208,7 @@ VMP_SLOOP
       L.hdr->suspend_action += n_susp;
     }
     __syncthreads();
-    const double r = big_tail<SPT, WL>(p, L, T, B, W, run0, dirty, k, term,
+    const double r = big_tail<SPT, SRC>(p, L, T, B, W, run0, dirty, k, term,
                                    last && o.obs ? o.obs + (int64_t)e * p.D : nullptr, last,
                                    o.policy >= 0, e
                                    STAMP_ARGS);
@@ -1194,7 +1216,7 @@ VMP_SLOOP
     ndone += term;
   }
   if (o.k_steps > 0) {
-    if (w0) svc_commit(L);
+    if (SRC != kSrcTrace && w0) svc_commit(L);
   }
   if (o.k_steps == 0 && o.policy >= 0 && o.act_out) {
     big_heuristic<SPT>(p, L, T, B, W, o.policy, o.act_out + (int64_t)e * V, nullptr STAMP_ARGS);
@@ -1257,15 +1279,16 @@ VMP_SLOOP
 }
 
 // host side: launch the instantiation for `spt` slots per thread
-template <bool ONE, bool WL>
+template <bool ONE, int SRC>
 static void launch_big_one(int spt, int n_env, size_t lds, hipStream_t s, const EnvParams &p,
                            const StepOut &o) {
+  constexpr bool WL = SRC == kSrcEnv, TR = SRC == kSrcTrace;
   const dim3 grid(n_env), block(kBigNT);
-  if (spt == 4) hipLaunchKernelGGL((k_env_big<4, ONE, WL>), grid, block, lds, s, p, o);
-  else if (spt == 8) hipLaunchKernelGGL((k_env_big<8, ONE, WL>), grid, block, lds, s, p, o);
-  else if (spt == 16) hipLaunchKernelGGL((k_env_big<16, ONE, WL>), grid, block, lds, s, p, o);
+  if (spt == 4) hipLaunchKernelGGL((k_env_big<4, ONE, WL, TR>), grid, block, lds, s, p, o);
+  else if (spt == 8) hipLaunchKernelGGL((k_env_big<8, ONE, WL, TR>), grid, block, lds, s, p, o);
+  else if (spt == 16) hipLaunchKernelGGL((k_env_big<16, ONE, WL, TR>), grid, block, lds, s, p, o);
   else
-  hipLaunchKernelGGL((k_env_big<kBigMaxSPT, ONE, WL>), grid, block, lds, s, p, o);
+  hipLaunchKernelGGL((k_env_big<kBigMaxSPT, ONE, WL, TR>), grid, block, lds, s, p, o);
 }
 
 }  // namespace vmp

@@ -493,21 +493,24 @@ __device__ __forceinline__ void predraw(const EnvParams &p, const Lds &L, const 
 // The Poisson records of env e: the handle's one pair, or (WL, the kernels of
 // handles with a per-env workload) the env's own pair of p.pois[N][2]. e is
 // wave-uniform, so this is scalar address arithmetic.
-template <bool WL>
+// (SRC: where an env's requests come from. kSrcConfig / kSrcEnv are the WL =
+// false / true instantiations; kSrcTrace never calls this.)
+constexpr int kSrcConfig = 0, kSrcEnv = 1, kSrcTrace = 2;
+template <int SRC>
 __device__ __forceinline__ const PoisConst *env_pois(const EnvParams &p, int e) {
-  return WL ? p.pois + 2 * (int64_t)e : p.pois;
+  return SRC == kSrcEnv ? p.pois + 2 * (int64_t)e : p.pois;
 }
 
 // Next planned runtime (rng4.poisson(L) + 1, env.py:289) for an accepted VM
 // of env e (the fallback reads that env's service-length record).
-template <bool WL>
+template <int SRC>
 __device__ __forceinline__ uint32_t svc_take(const EnvParams &p, const Lds &L, int e) {
   const int S = L.svcinfo[0], used = L.svcinfo[1];
   uint32_t x;
   if (used < S) {
     x = L.svc[used];
   } else {
-    x = svc_fallback(L.svcfb, &L.hdr->rng[3][2], env_pois<WL>(p, e) + 1);
+    x = svc_fallback(L.svcfb, &L.hdr->rng[3][2], env_pois<SRC>(p, e) + 1);
   }
   wsync();
   if (lane_id() == 0) L.svcinfo[1] = used + 1;
@@ -532,6 +535,50 @@ __device__ __forceinline__ void svc_commit(const Lds &L) {
     L.hdr->rng[3][0] = hi;
     L.hdr->rng[3][1] = lo;
   }
+  wsync();
+}
+
+// ---- trace-fed requests (kSrcTrace: the kernels of vmp_kernels_tr.hip) ----
+// A traced env draws nothing: the step at timestep s + 1 is offered the
+// requests [offs[s], offs[s+1]) of its trace (none from step `steps` on), so
+// the prologue's draws are replaced by one lane-parallel load of the launch's
+// offsets. The per-launch draw region (off_pre) is idle on this path: its first
+// 512 B (svcst) stage up to 64 packed requests, and svcfb[0] holds the index
+// of the current step's first request (a dropped request is consumed: every
+// step advances it by its whole arrival count).
+__device__ __forceinline__ TraceDesc env_trace(const EnvParams &p, int e) {
+  const TraceDesc *d = reinterpret_cast<const TraceDesc *>(p.pois) + e;  // e: wave-uniform
+  return TraceDesc{d->offs, d->req, d->steps, 0};
+}
+__device__ __forceinline__ int rq_cc(uint64_t rq) { return (int)((rq >> 16) & 0xFFu); }
+__device__ __forceinline__ int rq_cm(uint64_t rq) { return (int)((rq >> 24) & 0xFFu); }
+__device__ __forceinline__ uint32_t rq_rt(uint64_t rq) { return (uint32_t)(rq >> 32); }
+
+// L.arr[0..K) of a launch that starts at the header's timestep, and the first
+// step's first 64 requests staged (the accept loop of step 0 finds them there).
+// Every index is clamped into [0, steps], so no load is conditional.
+__device__ __forceinline__ void trace_preload(const Lds &L, const TraceDesc &d, int K) {
+  const int lane = lane_id();
+  const int64_t GLBP *offs = gptr(d.offs);
+  const int64_t ts = L.hdr->timestep;
+  const int64_t s0 = ts > 1 ? ts - 1 : 0;
+  uint64_t first = 0;
+  int a0 = 0;
+#pragma unroll 1
+  for (int k0 = 0; k0 < K; k0 += 64) {
+    const int k = k0 + lane;
+    const int64_t i0 = s0 + k < d.steps ? s0 + k : d.steps;
+    const int64_t i1 = i0 < d.steps ? i0 + 1 : d.steps;
+    const int64_t o0 = offs[i0], o1 = offs[i1];
+    if (k < K) L.arr[k] = (int32_t)(o1 - o0);  // < 2^31 per trace (trace_check)
+    if (k0 == 0) {
+      first = readlane_u64((uint64_t)o0, 0);
+      a0 = __builtin_amdgcn_readlane((int)(o1 - o0), 0);
+    }
+  }
+  const uint64_t GLBP *req = gptr(d.req);
+  L.svcst[lane] = lane < a0 ? req[first + (uint64_t)lane] : 0ull;
+  if (lane == 0) L.svcfb[0] = first;
   wsync();
 }
 

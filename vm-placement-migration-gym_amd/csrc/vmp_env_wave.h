@@ -262,7 +262,7 @@ __device__ __forceinline__ void external_apply(const EnvParams &p, const Lds &L,
 // waiting: remaining <= 1, i.e. placed now it finishes now), accepted words are
 // stored at once through `vmo`, and the caller fixes the finish keys of placed /
 // suspended VMs in memory; rem[] is then unused.
-template <int VPT, bool LAZY, bool WL>
+template <int VPT, bool LAZY, int SRC>
 __device__ __forceinline__ double env_tail(const EnvParams &p, const Lds &L, const Tables &T,
                                            uint32_t (&wa)[VPT], uint32_t (&rem)[VPT],
                                            uint32_t run0, uint32_t fb, uint32_t &dirty,
@@ -348,11 +348,29 @@ __device__ __forceinline__ double env_tail(const EnvParams &p, const Lds &L, con
     // to_accept = the first k NULL slots; sizes popped from the rng1/rng2
     // sequences, planned runtimes from rng4 (env.py:276-290)
     Pcg r1 = ld_pcg(H, 0), r2 = ld_pcg(H, 1);
+    // (a traced env: the step's requests in order, 64 at a time through the
+    // staging words; the launch's first chunk was staged by trace_preload)
+    const uint64_t GLBP *req = nullptr;
+    if constexpr (SRC == kSrcTrace) req = gptr(env_trace(p, e).req) + L.svcfb[0];
 #pragma unroll 1
     for (int j = 0; j < k; j++) {
-      const int cc = (int)rint((p.seq_lo + p.seq_range * next_double(r1)) * 100.0);
-      const int cm = (int)rint((p.seq_lo + p.seq_range * next_double(r2)) * 100.0);
-      const uint32_t rr = svc_take<WL>(p, L, e);
+      int cc, cm;
+      uint32_t rr;
+      if constexpr (SRC == kSrcTrace) {
+        if ((j & 63) == 0 && (j | kstep) != 0) {
+          wsync();
+          L.svcst[lane] = j + lane < k ? req[j + lane] : 0ull;
+          wsync();
+        }
+        const uint64_t rq = L.svcst[j & 63];
+        cc = rq_cc(rq);
+        cm = rq_cm(rq);
+        rr = rq_rt(rq);
+      } else {
+        cc = (int)rint((p.seq_lo + p.seq_range * next_double(r1)) * 100.0);
+        cm = (int)rint((p.seq_lo + p.seq_range * next_double(r2)) * 100.0);
+        rr = svc_take<SRC>(p, L, e);
+      }
       const int v = L.nulls[j];
       if (lane == (v & 63)) {
 #pragma unroll
@@ -374,8 +392,10 @@ __device__ __forceinline__ double env_tail(const EnvParams &p, const Lds &L, con
         L.accm[j] = (uint8_t)cm;
       }
     }
-    st_pcg(H, 0, r1);
-    st_pcg(H, 1, r2);
+    if constexpr (SRC != kSrcTrace) {
+      st_pcg(H, 0, r1);
+      st_pcg(H, 1, r2);
+    }
   }
   wsync();
   STAMP(3);
@@ -495,6 +515,7 @@ __device__ __forceinline__ double env_tail(const EnvParams &p, const Lds &L, con
     H->total_requests += arrivals;
     H->served += n_term;
     H->dropped += arrivals - k;
+    if constexpr (SRC == kSrcTrace) L.svcfb[0] += (uint64_t)arrivals;  // dropped requests are consumed
     H->waiting_ratio = wr;
     if (kl) {
       H->tcm = tcm;
@@ -566,9 +587,12 @@ __device__ __forceinline__ void write_mask(const EnvParams &p, const Lds &L, con
 // is a separate instantiation so profiles tell it apart from fused rollouts.
 // EXT = true: the external-action step (vmp_step), its own kernel k_env_ext so
 // the heuristic's registers do not weigh on it and vice versa.
-// WL = true: the handle has a per-env workload (vmp_set_workload); the only
-// difference is where the env's Poisson constants are read from (env_pois).
-template <int VPT, bool ONE, bool EXT, bool WL>
+// SRC = kSrcEnv (WL = true): the handle has a per-env workload
+// (vmp_set_workload); the only difference is where the env's Poisson constants
+// are read from (env_pois). SRC = kSrcTrace: the handle has a trace
+// (vmp_set_trace); nothing is drawn, the prologue loads the launch's arrival
+// counts from the env's trace (trace_preload) and the accept loop its requests.
+template <int VPT, bool ONE, bool EXT, int SRC>
 __device__ __forceinline__ void env_body(const EnvParams &p, const StepOut &o) {
   extern __shared__ __align__(16) char lds[];
   __shared__ Tables T;
@@ -598,11 +622,16 @@ __device__ __forceinline__ void env_body(const EnvParams &p, const StepOut &o) {
   // env per workgroup (e is wave-uniform: scalar address arithmetic)
   static_assert(kEnvWavesPerBlock == 1, "Tables::pois holds one env's Poisson constants");
   constexpr int kPoisWords = (int)(2 * sizeof(PoisConst) / 4);
-  const uint32_t pw =
-      gptr(reinterpret_cast<const uint32_t *>(env_pois<WL>(p, e)))[threadIdx.x % kPoisWords];
+  uint32_t pw = 0;
+  if constexpr (SRC != kSrcTrace)
+    pw = gptr(reinterpret_cast<const uint32_t *>(env_pois<SRC>(p, e)))[threadIdx.x % kPoisWords];
+  // a traced env's descriptor instead: a function of e alone (scalar loads
+  // beside the header's, no link in the header -> offsets -> requests chain)
+  TraceDesc td{nullptr, nullptr, 0, 0};
+  if constexpr (SRC == kSrcTrace) td = env_trace(p, e);
   // this lane's PCG64 jump entry (lane-parallel draws), right behind the header
   U128 JA{0, 0}, JM{0, 0};
-  if (o.k_steps > 0) {
+  if (SRC != kSrcTrace && o.k_steps > 0) {
     const uint64_t GLBP *jt = gptr(p.jump + 4 * lane);
     JA = U128{jt[0], jt[1]};
     JM = U128{jt[2], jt[3]};
@@ -638,7 +667,8 @@ __device__ __forceinline__ void env_body(const EnvParams &p, const StepOut &o) {
     T.cent[i] = (double)i / 100.0;
     T.fcent[i] = (float)((double)i / 100.0);
   }
-  if (threadIdx.x < kPoisWords) reinterpret_cast<uint32_t *>(T.pois)[threadIdx.x] = pw;
+  if (SRC != kSrcTrace && threadIdx.x < kPoisWords)
+    reinterpret_cast<uint32_t *>(T.pois)[threadIdx.x] = pw;
   __syncthreads();
   if (e_raw >= p.N) return;
   if (lane < 32) reinterpret_cast<uint64_t LDSP *>(L.hdr)[lane] = hv;
@@ -655,7 +685,11 @@ __device__ __forceinline__ void env_body(const EnvParams &p, const StepOut &o) {
       if (j * 64 + lane < n_pm) L.cpu[j * 64 + lane] = pv[j];
   }
   // the draws need only the header: they run while the PM / VM loads land
-  if (o.k_steps > 0) predraw(p, L, T, o.k_steps, V, JA, JM);
+  if constexpr (SRC == kSrcTrace) {
+    if (o.k_steps > 0) trace_preload(L, td, o.k_steps);
+  } else {
+    if (o.k_steps > 0) predraw(p, L, T, o.k_steps, V, JA, JM);
+  }
 #ifdef VMP_STAMPS
   const uint64_t t_drawn = __builtin_amdgcn_s_memtime();
 #endif
@@ -779,7 +813,7 @@ __device__ __forceinline__ void env_body(const EnvParams &p, const StepOut &o) {
     }
     wsync();
     bool calm = false;
-    const double r = env_tail<VPT, ONE, WL>(p, L, T, wa, rem, run0, fb, dirty, vmo, k, EXT, quiet,
+    const double r = env_tail<VPT, ONE, SRC>(p, L, T, wa, rem, run0, fb, dirty, vmo, k, EXT, quiet,
                                         term, calm, has_ex, e STAMP_ARGS);
     // the next step's skip: nothing fit (1), or every placement was rejected
     // (2); a skipped step passes its kind on while nothing changes
@@ -787,7 +821,7 @@ __device__ __forceinline__ void env_body(const EnvParams &p, const StepOut &o) {
     if (o.reward && lane == 0) gptr(o.reward)[(int64_t)k * p.N + e] = r;
     ndone += term;
   }
-  if (o.k_steps > 0) svc_commit(make_lds(p, opaque_base(base)));
+  if (SRC != kSrcTrace && o.k_steps > 0) svc_commit(make_lds(p, opaque_base(base)));
   if (!EXT && o.k_steps == 0 && o.policy >= 0 && o.act_out) {
     // act only: decide on a scratch copy of the VM words; nothing is stored
     uint32_t wt[VPT];
@@ -865,19 +899,46 @@ __device__ __forceinline__ void env_body(const EnvParams &p, const StepOut &o) {
 
 template <int VPT, bool ONE, bool WL>
 __global__ __launch_bounds__(64 * kEnvWavesPerBlock, ONE ? VMP_WAVES_PER_EU_ONE : VMP_WAVES_PER_EU) void k_env(EnvParams p, StepOut o) {
-  env_body<VPT, ONE, false, WL>(p, o);
+  env_body<VPT, ONE, false, WL ? kSrcEnv : kSrcConfig>(p, o);
 }
 // VPT 1 (V <= 64, the PPO eval's config/10.yml): 4 waves per SIMD, so a
 // 4 096-env step is one round of waves on the 256 CUs (at 3, 131 VGPRs, a
 // third of the envs ran in a second round)
 template <int VPT, bool WL>
 __global__ __launch_bounds__(64 * kEnvWavesPerBlock, VPT == 1 ? 4 : VMP_WAVES_PER_EU_ONE) void k_env_ext(EnvParams p, StepOut o) {
-  env_body<VPT, true, true, WL>(p, o);
+  env_body<VPT, true, true, WL ? kSrcEnv : kSrcConfig>(p, o);
+}
+// The kernels of handles with a trace (vmp_set_trace), same launch bounds
+template <int VPT, bool ONE>
+__global__ __launch_bounds__(64 * kEnvWavesPerBlock, ONE ? VMP_WAVES_PER_EU_ONE : VMP_WAVES_PER_EU) void k_env_tr(EnvParams p, StepOut o) {
+  env_body<VPT, ONE, false, kSrcTrace>(p, o);
+}
+template <int VPT>
+__global__ __launch_bounds__(64 * kEnvWavesPerBlock, VPT == 1 ? 4 : VMP_WAVES_PER_EU_ONE) void k_env_ext_tr(EnvParams p, StepOut o) {
+  env_body<VPT, true, true, kSrcTrace>(p, o);
 }
 
 // One translation unit instantiates one workload variant: vmp_kernels.hip the
 // kernels of handles with the config's one workload, vmp_kernels_wl.hip
-// (VMP_ENV_WL = true) those of handles with a per-env workload.
+// (VMP_ENV_WL = true) those of handles with a per-env workload,
+// vmp_kernels_tr.hip (VMP_ENV_TR) those of handles with a trace.
+#ifdef VMP_ENV_TR
+template __global__ void k_env_ext_tr<1>(EnvParams, StepOut);
+template __global__ void k_env_ext_tr<2>(EnvParams, StepOut);
+template __global__ void k_env_ext_tr<4>(EnvParams, StepOut);
+template __global__ void k_env_ext_tr<8>(EnvParams, StepOut);
+template __global__ void k_env_ext_tr<16>(EnvParams, StepOut);
+template __global__ void k_env_tr<1, false>(EnvParams, StepOut);
+template __global__ void k_env_tr<1, true>(EnvParams, StepOut);
+template __global__ void k_env_tr<2, false>(EnvParams, StepOut);
+template __global__ void k_env_tr<2, true>(EnvParams, StepOut);
+template __global__ void k_env_tr<4, false>(EnvParams, StepOut);
+template __global__ void k_env_tr<4, true>(EnvParams, StepOut);
+template __global__ void k_env_tr<8, false>(EnvParams, StepOut);
+template __global__ void k_env_tr<8, true>(EnvParams, StepOut);
+template __global__ void k_env_tr<16, false>(EnvParams, StepOut);
+template __global__ void k_env_tr<16, true>(EnvParams, StepOut);
+#else
 #ifndef VMP_ENV_WL
 #define VMP_ENV_WL false
 #endif
@@ -896,6 +957,7 @@ template __global__ void k_env<8, false, VMP_ENV_WL>(EnvParams, StepOut);
 template __global__ void k_env<8, true, VMP_ENV_WL>(EnvParams, StepOut);
 template __global__ void k_env<16, false, VMP_ENV_WL>(EnvParams, StepOut);
 template __global__ void k_env<16, true, VMP_ENV_WL>(EnvParams, StepOut);
+#endif  // VMP_ENV_TR
 
 }  // namespace vmp
 

@@ -23,6 +23,11 @@ template <int VPT, bool ONE, bool WL = false>
 __global__ void k_env(EnvParams p, StepOut o);
 template <int VPT, bool WL = false>
 __global__ void k_env_ext(EnvParams p, StepOut o);
+// the kernels of handles with a trace (vmp_set_trace): vmp_kernels_tr.hip
+template <int VPT, bool ONE>
+__global__ void k_env_tr(EnvParams p, StepOut o);
+template <int VPT>
+__global__ void k_env_ext_tr(EnvParams p, StepOut o);
 __global__ void k_rank(EnvParams p, int64_t *rank);
 __global__ void k_target_means_lds(EnvParams p);
 __global__ void k_reset(EnvParams p, const int64_t *seeds, const uint8_t *env_mask, float *obs);
@@ -39,6 +44,8 @@ void launch_big_env(int spt, bool one, int n_env, size_t lds, hipStream_t s, con
                     const StepOut &o);
 void launch_big_env_wl(int spt, bool one, int n_env, size_t lds, hipStream_t s,
                        const EnvParams &p, const StepOut &o);  // vmp_kernels_wl.hip
+void launch_big_env_tr(int spt, bool one, int n_env, size_t lds, hipStream_t s,
+                       const EnvParams &p, const StepOut &o);  // vmp_kernels_tr.hip
 int big_occupancy(int spt, size_t lds, int *static_lds);
 
 int64_t quiet_violations_take();

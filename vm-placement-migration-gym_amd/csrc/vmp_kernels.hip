@@ -51,8 +51,8 @@ int64_t quiet_violations_take() {
 // host side: the block kernel's launcher (vmp_capi.cpp)
 void launch_big_env(int spt, bool one, int n_env, size_t lds, hipStream_t s, const EnvParams &p,
                     const StepOut &o) {
-  if (one) launch_big_one<true, false>(spt, n_env, lds, s, p, o);
-  else launch_big_one<false, false>(spt, n_env, lds, s, p, o);
+  if (one) launch_big_one<true, kSrcConfig>(spt, n_env, lds, s, p, o);
+  else launch_big_one<false, kSrcConfig>(spt, n_env, lds, s, p, o);
 }
 // workgroups per CU of the per-step block kernel at `lds` dynamic bytes, and
 // its static LDS

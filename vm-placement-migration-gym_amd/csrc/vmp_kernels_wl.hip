@@ -28,8 +28,8 @@ namespace vmp {
 
 void launch_big_env_wl(int spt, bool one, int n_env, size_t lds, hipStream_t s,
                        const EnvParams &p, const StepOut &o) {
-  if (one) launch_big_one<true, true>(spt, n_env, lds, s, p, o);
-  else launch_big_one<false, true>(spt, n_env, lds, s, p, o);
+  if (one) launch_big_one<true, kSrcEnv>(spt, n_env, lds, s, p, o);
+  else launch_big_one<false, kSrcEnv>(spt, n_env, lds, s, p, o);
 }
 
 }  // namespace vmp

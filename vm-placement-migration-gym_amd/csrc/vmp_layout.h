@@ -94,6 +94,20 @@ struct PoisConst {
   int32_t tab_n;
 };
 
+// Trace-driven workload (vmp_set_trace): env e's entry of the device table
+// TraceDesc [N] that rides in EnvParams::pois while the handle has a trace (the
+// trace kernels of vmp_kernels_tr.hip read it instead of Poisson constants).
+// The step run at timestep s + 1 receives the requests [offs[s], offs[s+1]) of
+// `req` (none from step `steps` on). A request is the slot word's size bits
+// (cpu << 16 | mem << 24, hundredths) in the low word, the runtime in the high.
+struct alignas(32) TraceDesc {
+  const int64_t *offs;  // i64 [steps + 1], offs[0] = 0, non-decreasing
+  const uint64_t *req;  // u64 [offs[steps]]
+  int64_t steps;
+  int64_t pad;
+};
+static_assert(sizeof(TraceDesc) == 32, "TraceDesc is one 32-B record per env");
+
 struct EnvParams {
   int32_t N, P, V, A, D, W32;  // W32 = ceil(A/32) mask words per VM row
   int32_t reward, cap_target_util, eval_mode, pad0;
@@ -102,7 +116,8 @@ struct EnvParams {
   double beta, seq_lo, seq_range;
   // device copy: [0] arrivals, [1] service lengths, one pair for every env;
   // once the handle has a per-env workload (vmp_set_workload) [N][2], env e's
-  // pair at pois + 2 e, read by the WL = true instantiations of the step kernels
+  // pair at pois + 2 e, read by the WL = true instantiations of the step kernels;
+  // while the handle has a trace (vmp_set_trace) the TraceDesc [N] table instead
   const PoisConst *pois;
   uint64_t *stamps;       // [N][8] phase clocks (diagnostic builds only)
   uint32_t *vmw;          // [N][vm_pitch(V)] (slot words | time words per 64-slot block)

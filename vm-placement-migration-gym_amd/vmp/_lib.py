@@ -13,7 +13,8 @@ POLICIES = {"firstfit": 0, "bestfit": 1}
 
 EXPORTS = (
     "vmp_abi_version", "vmp_last_error", "vmp_create", "vmp_destroy", "vmp_set_stream",
-    "vmp_set_eval", "vmp_dims", "vmp_set_workload", "vmp_get_workload", "vmp_reset", "vmp_step",
+    "vmp_set_eval", "vmp_dims", "vmp_set_workload", "vmp_get_workload", "vmp_set_trace",
+    "vmp_clear_trace", "vmp_trace_info", "vmp_reset", "vmp_step",
     "vmp_heuristic_act", "vmp_heuristic_act_obs",
     "vmp_heuristic_step", "vmp_rollout_heuristic", "vmp_mask", "vmp_mask_bool", "vmp_get_obs",
     "vmp_get_counters", "vmp_get_stats", "vmp_get_state", "vmp_get_rank", "vmp_gae",
@@ -36,6 +37,12 @@ class VmpConfig(ctypes.Structure):
                 ("seed", ctypes.c_int64), ("reward_function", ctypes.c_int32),
                 ("sequence", ctypes.c_int32), ("cap_target_util", ctypes.c_int32),
                 ("allow_null_action", ctypes.c_int32), ("beta", ctypes.c_double)]
+
+
+class VmpTrace(ctypes.Structure):
+    """`vmp_trace` (include/vmp.h): host arrays of one request trace."""
+    _fields_ = [("steps", ctypes.c_int64), ("offs", ctypes.c_void_p), ("cpu", ctypes.c_void_p),
+                ("mem", ctypes.c_void_p), ("runtime", ctypes.c_void_p)]
 
 
 def to_c_config(cfg):
@@ -79,6 +86,9 @@ def lib():
         "vmp_dims": (ctypes.c_int, [P, P, P, P, P, P]),
         "vmp_set_workload": (ctypes.c_int, [P, P, P]),
         "vmp_get_workload": (ctypes.c_int, [P, P, P]),
+        "vmp_set_trace": (ctypes.c_int, [P, i32, P, P]),
+        "vmp_clear_trace": (ctypes.c_int, [P]),
+        "vmp_trace_info": (ctypes.c_int, [P, P, P, P, P]),
         "vmp_reset": (ctypes.c_int, [P, P, P, P]),
         "vmp_step": (ctypes.c_int, [P, P, P, P, P, P]),
         "vmp_step_mask": (ctypes.c_int, [P, P, P, P, P, P, P]),
@@ -129,7 +139,7 @@ def lib():
         if f is None:
             raise VmpError(f"libvmp lacks {name}")
         f.restype, f.argtypes = res, args
-    if L.vmp_abi_version() != 12:
+    if L.vmp_abi_version() != 13:
         raise VmpError("libvmp ABI mismatch")
     _lib = L
     return L

@@ -123,6 +123,57 @@ class BatchedVmEnv:
                                      s.ctypes.data_as(ctypes.c_void_p)))
         return a, s
 
+    def set_trace(self, traces, trace_of_env=None):
+        """Trace-driven workload (vmp_set_trace): env i replays
+        traces[trace_of_env[i]] (a `vmp.trace.Trace`, or a list of them; None
+        maps every env to trace 0) instead of drawing its requests: the step at
+        timestep s + 1 is offered the requests of the trace's step s, none once
+        the trace is over, and a dropped request is consumed (see vmp.trace).
+        The RNG streams rest; reset() rewinds every env to step 0 of its trace.
+        A graph captured before the first call must be recaptured; later calls
+        keep graphs valid and make them replay the new traces."""
+        from .trace import Trace
+        h = self._bind()
+        if isinstance(traces, Trace):
+            traces = [traces]
+        traces = list(traces)
+        if not traces or not all(isinstance(t, Trace) for t in traces):
+            raise ValueError("traces must be a Trace or a non-empty list of Trace")
+        arr = (_lib.VmpTrace * len(traces))()
+        for c, t in zip(arr, traces):
+            c.steps = t.steps
+            c.offs, c.cpu = t.offs.ctypes.data, t.cpu.ctypes.data
+            c.mem, c.runtime = t.mem.ctypes.data, t.runtime.ctypes.data
+        m = None
+        if trace_of_env is not None:
+            m = np.ascontiguousarray(np.asarray(trace_of_env), dtype=np.int32)
+            if m.shape != (self.n_envs,):
+                raise ValueError(f"trace_of_env must have n_envs = {self.n_envs} entries")
+        pm = None if m is None else m.ctypes.data_as(ctypes.c_void_p)
+        with torch.cuda.device(self.device):
+            check(lib().vmp_set_trace(h, len(traces), ctypes.cast(arr, ctypes.c_void_p), pm))
+
+    def clear_trace(self):
+        """Back to the RNG workload (the per-env one if the env has it), the
+        streams where they stood (vmp_clear_trace)."""
+        with torch.cuda.device(self.device):
+            check(lib().vmp_clear_trace(self._bind()))
+
+    def trace_info(self):
+        """None without a trace, else dict(n_traces, trace_of_env int32 [n_envs],
+        steps int64 [n_traces], requests int64 [n_traces])."""
+        h = self._bind()
+        n = ctypes.c_int32()
+        check(lib().vmp_trace_info(h, ctypes.byref(n), None, None, None))
+        if n.value == 0:
+            return None
+        m = np.empty(self.n_envs, np.int32)
+        st, rq = np.empty(n.value, np.int64), np.empty(n.value, np.int64)
+        check(lib().vmp_trace_info(h, None, m.ctypes.data_as(ctypes.c_void_p),
+                                   st.ctypes.data_as(ctypes.c_void_p),
+                                   rq.ctypes.data_as(ctypes.c_void_p)))
+        return dict(n_traces=n.value, trace_of_env=m, steps=st, requests=rq)
+
     def reset(self, seeds=None, mask=None, obs=True):
         """reset(seed) for every env (or those where mask is true). seeds=None is
         reset(seed=None): the RNG streams continue (env.py:181-182)."""
@@ -293,7 +344,9 @@ class BatchedVmEnv:
         PM and VM words) as a device u8 tensor; `restore` on an env of the same
         config and n_envs continues bit-exactly from here. torch.save it for a
         resumable run (SURVEY §5). An env given a per-env workload appends it;
-        such a snapshot restores only into an env with the same workload."""
+        such a snapshot restores only into an env with the same workload. A
+        traced env's snapshot carries a hash of its traces and map and restores
+        only into an env replaying the same ones."""
         h = self._bind()
         n = ctypes.c_int64()
         check(lib().vmp_snapshot_bytes(h, ctypes.byref(n)))

@@ -67,6 +67,14 @@ class VmEnv(_GymEnv):
         self._b = BatchedVmEnv(cfg, 1, seeds=[int(config.seed)], device=device)
         self.reset(config.seed)
 
+    def set_trace(self, trace):
+        """Replay `trace` (vmp.trace.Trace) instead of drawing requests
+        (BatchedVmEnv.set_trace); None goes back to the RNG workload."""
+        if trace is None:
+            self._b.clear_trace()
+        else:
+            self._b.set_trace(trace)
+
     # ------------------------------------------------------- state views
     def _st(self):
         return {k: v[0].cpu().numpy() for k, v in self._b.state().items()}

@@ -13,6 +13,7 @@ comes back to the host. This replaces the reference's process fan-out
     python -m vmp.exp vm_size                              # exp_vm_size.py summary
     python -m vmp.exp reward --agents ppo --weights 'w/ppo-{reward}.pt'   # exp_reward.py
     python -m vmp.exp migration_ratio --agents bestfit,ppo --weights 'w/ppo-{reward}.pt'
+    python -m vmp.exp paired --trace a.npz,b.npz           # every agent on the same requests
 
 Rows are printed in exp_suspension.py's CSV layout (exp_suspension.py:51-58):
 Agent, Load, Service Length, Total Served, Valid Suspend Actions, Valid
@@ -213,6 +214,57 @@ def suspension_sweep(agents=("firstfit", "bestfit"), loads=None, lengths=None, s
     return [suspension_row(c, r) for c, r in zip(cells, res)]
 
 
+# ------------------------------------------------------------ paired comparison
+PAIRED_HEADER = ("Agent, Trace, Steps, Requests, Total Served, Valid Suspend Actions, "
+                 "Valid Actions, Life, Average Pending, Average Slowdown, Max Slowdown")
+
+
+def paired_row(agent, index, trace, summary):
+    """One (agent, trace) row: suspension_row's metric columns for one env."""
+    susp, placed = summary["total suspend actions"], summary["total place actions"]
+    life = summary["_mean_life"]  # NaN for an env no VM ever lived in (an empty trace)
+    return "%s,%d,%d,%d,%d,%d,%d,%s,%.3f,%.3f,%.3f" % (
+        agent, index, trace.steps, trace.requests, summary["total served VMs"], susp,
+        susp + placed, "%d" % life if life == life else "nan", summary["_mean_pending"],
+        summary["_mean_slowdown"], summary["_max_slowdown"])
+
+
+def paired_sweep(traces, agents=("firstfit", "bestfit"), config=None, eval_steps=None,
+                 weights=None, device="cuda:0"):
+    """Every agent on the SAME requests: one handle per agent whose env i replays
+    traces[i] (BatchedVmEnv.set_trace), the device recorder on, eval_steps steps
+    (default: the longest trace). A traced env's requests do not depend on what
+    the policy did with the earlier ones, so the rows of one trace compare the
+    agents on one workload. One CSV row per (agent, trace), see PAIRED_HEADER."""
+    traces = list(traces)
+    cfg = dict(ENV100, reward_function="wr") if config is None else dict(config)
+    steps = int(eval_steps) if eval_steps is not None else max(t.steps for t in traces)
+    cfg["eval_steps"] = max(int(cfg.get("eval_steps", 0)), steps)
+    rows = []
+    for name in agents:
+        if name != "ppo" and name not in HEURISTICS:
+            raise ValueError(f"agent {name!r} has no batched GPU path")
+        env = BatchedVmEnv(Config(**cfg), len(traces), device=device)
+        env.set_trace(traces, np.arange(len(traces)))  # before any capture: it switches kernels
+        env.eval(True)
+        env.reset()
+        env.record(True)
+        if name == "ppo":
+            from .ppo import ActStepGraph, PPOAgent, PPOConfig
+            ag = PPOAgent(env, PPOConfig(**PPO100))
+            ag.load_model(weights)
+            ag.eval(True)
+            graph = ActStepGraph(ag, warmup=0)
+            for _ in range(steps):
+                graph.replay()
+        else:
+            env.rollout(name, steps)
+        summ = env.record_summary()
+        env.close()
+        rows += [paired_row(name, i, t, s) for i, (t, s) in enumerate(zip(traces, summ))]
+    return rows
+
+
 # ------------------------------------------------------------ exp_performance
 PERFORMANCE_HEADER = ("Agent, Load, Return, Drop Rate, Served VM, Suspend Actions, CPU Mean, "
                       "CPU Variance, Memory Mean, Memory Variance, Pending Rate, Waiting Ratio, "
@@ -369,7 +421,7 @@ def migration_sweep(cells, eval_steps=None):
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("experiment", choices=["suspension", "performance", "performance_small",
-                                           "vm_size", "reward", "migration_ratio"])
+                                           "vm_size", "reward", "migration_ratio", "paired"])
     ap.add_argument("--agents", default="firstfit,bestfit")
     ap.add_argument("--weights", default=None, help="PPO weights (.pt) for agent ppo")
     ap.add_argument("--seeds", default=None, help="comma list (default: the driver's seeds)")
@@ -380,12 +432,29 @@ def main(argv=None):
     ap.add_argument("--eval-steps", type=int, default=None)
     ap.add_argument("--merge", action="store_true",
                     help="suspension: one handle per heuristic agent, a per-env workload per cell")
+    ap.add_argument("--trace", default=None, help="paired: comma list of Trace .npz files")
+    ap.add_argument("--config", default=None,
+                    help="paired: YAML with an `environment:` section (default config/100.yml's, wr)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args(argv)
     agents = a.agents.split(",")
     seeds = None if a.seeds is None else [int(x) for x in a.seeds.split(",")]
     loads = None if a.loads is None else [float(x) for x in a.loads.split(",")]
-    if a.experiment == "suspension":
+    if a.experiment == "paired":
+        from .trace import Trace
+        if not a.trace:
+            ap.error("paired needs --trace FILE.npz[,FILE.npz...]")
+        cfg = None
+        if a.config:
+            import yaml
+            with open(a.config) as f:
+                cfg = dict(yaml.safe_load(f)["environment"])
+            if a.reward:
+                cfg["reward_function"] = a.reward
+        header = PAIRED_HEADER
+        rows = paired_sweep([Trace.load(p) for p in a.trace.split(",")], agents=agents, config=cfg,
+                            eval_steps=a.eval_steps, weights=a.weights)
+    elif a.experiment == "suspension":
         header = SUSPENSION_HEADER
         rows = suspension_sweep(
             agents=agents, loads=loads,

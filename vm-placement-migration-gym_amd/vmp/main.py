@@ -7,7 +7,9 @@ Same flags, same YAML schema (`environment:` section -> Config, `agents:
 load-or-learn-then-save weights logic (main.py:65-77) and `agent.test` eval
 (main.py:79-82); `run(Args)` returns the Record as the reference's does (the
 exp_* drivers call it). Additions: `--envs N` trains PPO on N batched GPU envs
-(the reference trains one), `--device`. The drlvmp / convex / rainbow agents
+(the reference trains one), `--device`, and `--trace FILE.npz`: the env replays
+the requests of a vmp.trace.Trace file instead of drawing them (training and
+eval alike; `--envs N` training replays it on every env). The drlvmp / convex / rainbow agents
 are out of scope and raise.
 """
 import argparse
@@ -36,6 +38,7 @@ class Args:
     debug: bool = False
     envs: int = 1
     device: str = "cuda"
+    trace: str = None
 
 
 def _known(cls, d):
@@ -71,6 +74,11 @@ def run(args: Args):
         torch.cuda.manual_seed_all(seed)
 
     env = VmEnv(Config(**_known(Config, env_config)), device=args.device)
+    trace = None
+    if args.trace:
+        from .trace import Trace
+        trace = Trace.load(args.trace)
+        env.set_trace(trace)
     agent = make_agent(args.agent, env, agent_config)
     if args.logdir and args.jobname:
         agent.set_log(jobname=args.jobname, logdir=args.logdir)
@@ -80,6 +88,8 @@ def run(args: Args):
             # batched training on N GPU envs, then the weights go to the N=1 agent
             from .batched import BatchedVmEnv
             benv = BatchedVmEnv(env.config, args.envs, device=env._b.device)
+            if trace is not None:
+                benv.set_trace(trace)
             trainer = make_agent("ppo", benv, agent_config)
             trainer.learn()
             agent.model.load_state_dict(trainer.model.state_dict())
@@ -126,13 +136,15 @@ def parse(argv=None):
                    help="Do not print summary of the model")
     p.add_argument("--envs", type=int, default=1, help="batched GPU envs for PPO training")
     p.add_argument("--device", default="cuda")
+    p.add_argument("--trace", default=None,
+                   help="replay the requests of this Trace .npz instead of drawing them")
     a = p.parse_args(argv)
     import yaml
     with open(a.config) as f:
         cfg = yaml.safe_load(f)
     return Args(agent=a.agent, reward=a.reward, config=cfg, logdir=a.logdir, output=a.output,
                 silent=a.silent, jobname=a.jobname, weightspath=a.weightspath, eval=a.eval,
-                debug=a.debug, envs=a.envs, device=a.device)
+                debug=a.debug, envs=a.envs, device=a.device, trace=a.trace)
 
 
 if __name__ == "__main__":

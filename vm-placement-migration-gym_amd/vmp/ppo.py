@@ -693,6 +693,9 @@ class PPOTrainer:
         import torch.distributed as dist
         self.agent, self.cfg = agent, agent.config
         self.env, self.model = agent.benv, agent.model
+        if self.cfg.load_range is not None and self.env.trace_info() is not None:
+            raise ValueError("load_range sets per-env arrival rates, which a traced env "
+                             "(set_trace) does not draw from: use one or the other")
         self.gae = agent._gae_impl if agent._gae_impl is not None else H.gae
         use = distributed and dist.is_available() and dist.is_initialized()
         self.dist = dist if use else None
