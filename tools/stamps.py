@@ -44,7 +44,8 @@ names = ["loop-end", "act+apply(rest)", "run_vms", "accept", "stats(rest)+reward
          "pro:start->hdr/pm loaded", "pro:predraw", "pro:VM words loaded",
          "heur:prep", "heur:fitmax+hits", "heur:earliest", "apply:requery", "apply:scan+place",
          "apply:f32 update", "-", "apply:fitmax"]
-tot = st.sum(1) - st[:, 7] - st[:, 9]
+IDLE_N, IDLE_WALL, IDLE_CYC = 8, 10, 22  # vmp_stamps.h: launches that met the idle predicate
+tot = st.sum(1) - st[:, 7] - st[:, 9] - st[:, [IDLE_N, IDLE_WALL, IDLE_CYC]].sum(1)
 c1 = env.counters().cpu().numpy()
 d = (c1 - c0).sum(0) / (N * K)
 print(f"N={N} V={V} steps {FF + 1}-{FF + K}: mean cycles per env-step (per wave) = "
@@ -59,6 +60,17 @@ wall_us = st[:, 7] / 1000 / 100.0  # 100 MHz realtime ticks
 cyc = st[:, 9]
 print(f"wave lifetime: {wall_us.mean():.1f} us wall (mean), {cyc.mean():.0f} shader cycles -> "
       f"{cyc.mean() / wall_us.mean() / 1e3:.2f} GHz")
+# launches that met the idle-step predicate (they took the idle path and
+# stamp no phase above), and the others
+n_idle, n_all = st[:, IDLE_N].sum() * K, float(N * K)
+if 0 < n_idle < n_all:
+    us = lambda ticks, n: ticks * K / 1000 / 100.0 / n  # noqa: E731
+    print(f"idle-step waves: share {n_idle / n_all:.3f}, mean lifetime {us(st[:, IDLE_WALL].sum(), n_idle):.2f} us "
+          f"({st[:, IDLE_CYC].sum() * K / n_idle:.0f} cycles); other waves "
+          f"{us(st[:, 7].sum() - st[:, IDLE_WALL].sum(), n_all - n_idle):.2f} us "
+          f"({(st[:, 9].sum() - st[:, IDLE_CYC].sum()) * K / (n_all - n_idle):.0f} cycles)")
+else:
+    print(f"idle-step waves: share {n_idle / n_all:.3f}")
 print("mean waiting", (pl == 100).sum(1).mean(), "running", (pl < 100).sum(1).mean())
 q = np.percentile(wall_us, [10, 50, 90, 99])
 print(f"wave lifetime percentiles (us): p10 {q[0]:.1f} p50 {q[1]:.1f} p90 {q[2]:.1f} p99 {q[3]:.1f} "

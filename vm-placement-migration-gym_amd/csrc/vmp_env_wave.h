@@ -583,6 +583,89 @@ __device__ __forceinline__ void write_mask(const EnvParams &p, const Lds &L, con
   }
 }
 
+// ---- the idle step of a per-step heuristic launch -------------------------
+// A per-step launch whose header says that the step changes nothing of the
+// env but its clock: the heuristic is skipped (EnvHdr::pad bit 62 or 60, see
+// heuristic_apply), the previous per-step launch left no NULL slot (bit 63
+// set, bit 32 clear: no request can be accepted) and the smallest running
+// finish key nf is past this step (nf > t + 1: no VM finishes). Such a step
+// draws its arrival count and drops all of it, repeats the stored wr reward
+// and re-emits the observation; the VM words, the PM words, rng1/2/4 and the
+// whole pad word stay as they are (the hint carries nf, bit 32 stays 0, bits
+// 60-62 carry over: the step is calm and quiet). It is the predicate of
+// env_body's skip_time plus the conditions under which nothing else leaves
+// the step (wr reward, no actions / validity flags / mask returned). The pad
+// word must be exactly what the general path would write back (one of bits
+// 62 / 60, bits 33-59 clear), so leaving it alone is the same store.
+// Wave-uniform (readfirstlane: a scalar branch).
+// 2P <= 256: idle_body reads the PM words from LDS and would serve any P; the
+// limit is the one the path was specified and is tested with (larger P keeps
+// the general path, tests/test_gpu_idle_step.py row p130v64).
+// The skip_time terms are written out here and again in env_body, on
+// purpose: env_body's own expression stays where the parent has it (moving
+// it moves the general path's register allocation), and a
+// step that is idle here is one env_body would give skip_time; the
+// twin-handle tests hold the two together.
+__device__ __forceinline__ bool idle_step(const EnvParams &p, const StepOut &o, const Lds &L) {
+#ifdef VMP_CHECK_QUIET
+  return false;  // as skip_time: the audited state must evolve as the product's
+#else
+  const uint64_t ph = L.hdr->pad;
+  const uint32_t t32 = (uint32_t)L.hdr->timestep;
+  const uint32_t nf = (uint32_t)ph;
+  const bool q1 = (ph >> 62) & 1u, q2 = (ph >> 60) & 1u;
+  const bool idle = o.k_steps == 1 && p.reward == 0 && !o.act_out && !o.valid && !o.mask_bits &&
+                    2 * p.P <= 256 && (ph >> 63) && q1 != q2 &&
+                    (ph & 0x0FFFFFFF00000000ull) == 0 && nf != 0u && (int32_t)(nf - t32) > 1;
+  return uni((int)idle) != 0;
+#endif
+}
+
+// The idle step itself, behind the general path's prologue (header, PM words
+// and the launch's draws are in LDS: L.arr[0] is the arrival count, rng3 is
+// advanced): env_tail's counters / reward / done, write_obs, and the 32-lane
+// header write-back (storing only the five changed words measured slower).
+template <int VPT>
+__device__ __forceinline__ void idle_body(const EnvParams &p, const StepOut &o, const Lds &L,
+                                          const float LDSP *fcent, int e,
+                                          const uint32_t (&wa)[VPT]) {
+  const int lane = lane_id();
+  const int V = p.V;
+  EnvHdr LDSP *H = L.hdr;
+  const int64_t a = L.arr[0];
+  const uint64_t ph = H->pad;
+  const int64_t ts = H->timestep;
+  const bool term = ts >= p.limit;
+  if (lane == 0) {
+    if (o.reward) gptr(o.reward)[e] = ((ph >> 61) & 1u) ? -H->waiting_ratio : 0.0;
+    if (o.done) gptr(o.done)[e] = (uint8_t)term;
+    if (o.done_count) gptr(o.done_count)[e] += (int64_t)term;
+  }
+  if (o.obs) {
+    float *obs = o.obs + (int64_t)e * p.D;
+#pragma unroll
+    for (int s = 0; s < VPT; s++) {
+      const int v = s * 64 + lane;
+      if (live(wa[s])) {
+        ST_NT(obs + v, (float)w_pl(wa[s]));
+        ST_NT(obs + V + v, fcent[w_cc(wa[s])]);
+        ST_NT(obs + 2 * V + v, fcent[w_cm(wa[s])]);
+      }
+    }
+    // L.cpu is [cpu P][memory P], the obs tail's order
+    for (int i = lane; i < 2 * p.P; i += 64) ST_NT(obs + 3 * V + i, (float)L.cpu[i]);
+  }
+  wsync();
+  if (lane == 0) {
+    H->timestep = ts + 1;
+    H->total_requests += a;
+    H->dropped += a;
+  }
+  wsync();
+  if (lane < 32)
+    gptr(reinterpret_cast<uint64_t *>(p.hdr + e))[lane] = reinterpret_cast<uint64_t LDSP *>(H)[lane];
+}
+
 // ONE = true is the per-step launch (k_steps == 1, the Base.test loop body); it
 // is a separate instantiation so profiles tell it apart from fused rollouts.
 // EXT = true: the external-action step (vmp_step), its own kernel k_env_ext so
@@ -712,6 +795,18 @@ __device__ __forceinline__ void env_body(const EnvParams &p, const StepOut &o) {
     st_acc[15] = st_prev - t_drawn;
   }
 #endif
+  // the idle step (see idle_step) leaves here: behind the prologue, which is
+  // the general path's own up to this point (no load depends on the branch).
+  // Traced envs keep the general path.
+  if constexpr (ONE && !EXT && SRC != kSrcTrace) {
+  if (idle_step(p, o, L)) {
+    idle_body<VPT>(p, o, L, (const float LDSP *)T.fcent, e, wa);
+#ifdef VMP_STAMPS
+    if (p.stamps && lane == 0) stamp_idle(p.stamps + (int64_t)e * kStamps, t_start, rt_start);
+#endif
+    return;
+  }
+  }
   bool term = false;
   int64_t ndone = 0;
   uint32_t dirty = 0;  // bit s: this lane's VM word s changed (stored at the end)

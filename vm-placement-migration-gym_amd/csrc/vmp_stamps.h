@@ -36,6 +36,22 @@ namespace vmp {
     if (p.stamps && st_acc && lane_id() == 0)                                 \
       for (int _i = 0; _i < kStamps; _i++) p.stamps[(int64_t)e * kStamps + _i] += st_acc[_i]; \
   } while (0)
+// k_env: a wave whose launch met the idle-step predicate (idle_step) says so
+// in three slots k_env stamps nowhere else: how many of the env's launches did,
+// and their share of slots 7 (wall time, x1000 100 MHz ticks) and 9 (shader
+// cycles). tools/stamps.py reads them.
+constexpr int kStampIdleN = 8, kStampIdleWall = 10, kStampIdleCyc = 22;
+// the idle path's record, straight to the env's row (it leaves before the
+// first STAMP; the prologue's three LDS slots are not flushed)
+__device__ __forceinline__ void stamp_idle(uint64_t *row, uint64_t t_start, uint64_t rt_start) {
+  const uint64_t wall = (__builtin_amdgcn_s_memrealtime() - rt_start) * 1000;
+  const uint64_t cyc = __builtin_amdgcn_s_memtime() - t_start;
+  row[7] += wall;
+  row[9] += cyc;
+  row[kStampIdleN] += 1;
+  row[kStampIdleWall] += wall;
+  row[kStampIdleCyc] += cyc;
+}
 #elif defined(VMP_WGTIME)
 // Workgroup timing build (k_env_big): thread 0 records the 100 MHz real-time
 // clock at every stamp point into a block LDS row; tools/wgtime.py reads it.

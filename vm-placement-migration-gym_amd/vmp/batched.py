@@ -240,13 +240,22 @@ class BatchedVmEnv:
         return a
 
     def heuristic_step(self, policy="firstfit", want_actions=False, want_valid=False,
-                       want_obs=True):
-        """act(obs) then step(action) in one launch (the Base.test loop body)."""
+                       want_obs=True, obs=None, reward=None, done=None):
+        """act(obs) then step(action) in one launch (the Base.test loop body).
+        obs f32[N,D] / reward f64[N] / done u8[N]: the caller's own contiguous
+        output buffers (as `step` takes them); allocated here when None."""
         h = self._bind()
         a = self._empty((self.n_envs, self.V), torch.int32) if want_actions else None
-        obs = self._empty((self.n_envs, self.D), torch.float32) if want_obs else None
-        reward = self._empty((self.n_envs,), torch.float64)
-        done = self._empty((self.n_envs,), torch.uint8)
+        for t, shape, dt in ((obs, (self.n_envs, self.D), torch.float32),
+                             (reward, (self.n_envs,), torch.float64),
+                             (done, (self.n_envs,), torch.uint8)):
+            if t is not None and (t.shape != shape or t.dtype != dt or not t.is_contiguous()
+                                  or t.device != self.device):
+                raise ValueError(f"output buffer must be contiguous {dt} {shape} on {self.device}")
+        if obs is None and want_obs:
+            obs = self._empty((self.n_envs, self.D), torch.float32)
+        reward = self._empty((self.n_envs,), torch.float64) if reward is None else reward
+        done = self._empty((self.n_envs,), torch.uint8) if done is None else done
         valid = self._empty((self.n_envs, self.V), torch.uint8) if want_valid else None
         check(lib().vmp_heuristic_step(h, _lib.POLICIES[policy], ptr(a), ptr(obs), ptr(reward),
                                        ptr(done), ptr(valid)))
