@@ -481,10 +481,12 @@ int block_threads(int V, int G) {
     hipLaunchKernelGGL((KERN<GG, EE>), dim3(a.B), dim3(block_threads(a.V, GG)), 0, st, a); \
     return hipGetLastError();                                                            \
   }
+// the seven (G, E) pick_g / pick_e can give: G = 16 starts at A = 65 (need 5)
+// and G = 64 at A = 257 (need 5), so (16, 4) and (64, 4) do not exist
 #define VMP_HEAD_ALL(KERN)                                                               \
   VMP_HEAD_CASE(KERN, 4, 4) VMP_HEAD_CASE(KERN, 4, 8) VMP_HEAD_CASE(KERN, 4, 16)         \
-  VMP_HEAD_CASE(KERN, 16, 4) VMP_HEAD_CASE(KERN, 16, 8) VMP_HEAD_CASE(KERN, 16, 16)      \
-  VMP_HEAD_CASE(KERN, 64, 4) VMP_HEAD_CASE(KERN, 64, 8) VMP_HEAD_CASE(KERN, 64, 16)
+  VMP_HEAD_CASE(KERN, 16, 8) VMP_HEAD_CASE(KERN, 16, 16)                                 \
+  VMP_HEAD_CASE(KERN, 64, 8) VMP_HEAD_CASE(KERN, 64, 16)
 
 bool use_tiles(const HeadArgs &a) {
   return a.A <= kTileMaxA && ((uintptr_t)a.logits & 15) == 0 &&
