@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define VMP_ABI_VERSION 13
+#define VMP_ABI_VERSION 14
 
 #define VMP_OK 0
 #define VMP_EINVAL (-1)
@@ -72,6 +72,19 @@ extern "C" {
 #define VMP_NREC 19
 #define VMP_REC_XMAX 64
 #define VMP_REC_BINS 1001   /* pending / slowdown rates x1000: 0 .. 1000 */
+/* per-request outcome log (vmp_reqlog_read): one int32[VMP_RQ_NF] row per request id */
+#define VMP_RQ_SLOT 0       /* -2 not observed, -1 dropped, >= 0 the slot it took */
+#define VMP_RQ_ARRIVED 1    /* timestep of the step that offered it (dropped ones too) */
+#define VMP_RQ_PLACED 2     /* timestep of its first valid placement, 0 = not yet */
+#define VMP_RQ_FINISHED 3   /* timestep of the step whose _run_vms finished it, 0 = not yet */
+#define VMP_RQ_SUSPENDS 4   /* valid suspend actions on it */
+#define VMP_RQ_WAIT_STEPS 5 /* steps that left it at WAIT, the arrival step included */
+#define VMP_RQ_NF 6
+/* ... and its per-env meta, int64[VMP_RQ_NMETA] */
+#define VMP_RQ_FIRST 0      /* total_requests when the env's log started */
+#define VMP_RQ_NEXT 1       /* total_requests now: the ids observed are [FIRST, NEXT) */
+#define VMP_RQ_LOST 2       /* requests whose id was >= capacity: not logged */
+#define VMP_RQ_NMETA 3
 /* actor-head modes (vmp_policy_head) */
 #define VMP_HEAD_SAMPLE 0 /* Network.get_action(obs, action=None, mask) (ppo.py:115-126) */
 #define VMP_HEAD_GIVEN 1  /* Network.get_action(obs, action, mask): log_prob/entropy only */
@@ -447,6 +460,48 @@ int vmp_record_enable(vmp_handle *h, int32_t on);
  * over every VM life incl. the open ones; sums f64[n_env][VMP_NREC]. The
  * Record.get_summary values follow from these (vmp/record.py). */
 int vmp_record_read(vmp_handle *h, uint32_t *hist, double *sums);
+
+/* Per-request outcome log on the device: what happened to request j of an env, for paired
+ * comparisons of policies on one trace (vmp_set_trace), or on any workload. The id of a
+ * request is its ordinal among the requests offered to the env since its last reset: the
+ * value of total_requests before it is counted (on a traced env reset at step 0, its index
+ * in the trace: drops are consumed). Per env the log holds `capacity` rows
+ * int32[VMP_RQ_NF] indexed by id, updated by one more kernel after every vmp_step /
+ * vmp_step_mask / vmp_heuristic_step; vmp_rollout_heuristic runs one step per launch while
+ * the log is on, as it does for the recorder. t below is the env's timestep when the step
+ * starts (reset leaves 1; a traced step t offers trace step t - 1).
+ *   SLOT      -2: not observed (never offered, or offered before the log started);
+ *             -1: dropped; >= 0: the slot it took
+ *   ARRIVED   t of the step that offered it, set for dropped requests too
+ *   PLACED    t of the step whose action phase first placed it validly (0: not yet), so
+ *             PLACED - ARRIVED steps passed before its first placement
+ *   FINISHED  t of the step whose _run_vms finished it (0: not yet)
+ *   SUSPENDS  valid suspend actions on it
+ *   WAIT_STEPS steps that left it at WAIT, the arrival step included, so
+ *             WAIT_STEPS - (PLACED - ARRIVED) steps were spent suspended after placement
+ * Meta int64[VMP_RQ_NMETA] per env: FIRST = total_requests when the env's log started, NEXT =
+ * total_requests now, LOST = requests whose id was >= capacity (not logged; their VMs stay
+ * untracked).
+ *
+ * vmp_reqlog_enable: capacity = rows per env; 0 frees the log. Otherwise the log is
+ * (re)allocated and started from the current state: VMs already in the system are not
+ * tracked and ids below FIRST stay unobserved. capacity < 0, above 2^31 - 1 or of a byte
+ * size that does not fit returns VMP_EINVAL; a failed allocation VMP_EOOM, the handle (and
+ * an earlier log) exactly as before. With the recorder on as well, the two share the
+ * handle's scratch action / validity buffers. Stream-ordered behind the queued launches; it
+ * allocates, so it must not be made during capture, and a graph captured before it does not
+ * log and must be recaptured.
+ * With the log on, vmp_reset restarts the log of exactly the envs it resets, vmp_restore
+ * restarts every env's log (the log is not part of a snapshot), vmp_destroy frees it. (ABI 14) */
+int vmp_reqlog_enable(vmp_handle *h, int64_t capacity);
+/* Rows per env of the handle's log, 0 = off. */
+int vmp_reqlog_info(const vmp_handle *h, int64_t *capacity);
+/* Copy the log so far (non-destructive, stream-ordered): rows device
+ * int32[n_env][capacity][VMP_RQ_NF], meta device int64[n_env][VMP_RQ_NMETA], each nullable.
+ * VMP_ESTATE while the log is off. (On the device WAIT_STEPS of a VM that is waiting now is an
+ * open count, written at events only; the read closes it in the caller's copy with one small
+ * kernel, so the rows read are always the counts up to the last step.) */
+int vmp_reqlog_read(vmp_handle *h, int32_t *rows, int64_t *meta);
 
 /* Fault injection (tests only): the n-th device allocation made by the
  * library from now on fails as out of memory (n = 0: off). Drives the

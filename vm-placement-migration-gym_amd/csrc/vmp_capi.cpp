@@ -15,6 +15,7 @@
 #include "vmp_kernels.h"
 #include "vmp_layout.h"
 #include "vmp_record.h"
+#include "vmp_reqlog.h"
 #include "vmp_trace.h"
 
 using namespace vmp;
@@ -48,6 +49,10 @@ struct vmp_handle {
   int32_t *rec_act;   // scratch action / validity / reward when the caller passes none
   uint8_t *rec_valid;
   double *rec_reward;
+  // per-request outcome log (vmp_reqlog.hip), allocated by vmp_reqlog_enable; with the
+  // recorder on as well the two share rec_act / rec_valid
+  bool rq_on;
+  ReqArgs rq;
   // per-env workload (vmp_set_workload); all null / 0 for a handle never given one
   double *wl;           // host f64 [N][2]: arrival_rate, service_length of every env
   PoisConst *wl_rec;    // host mirror of pois_env
@@ -119,6 +124,24 @@ StepOut empty_out() {
 void refresh_params(vmp_handle *h) {
   h->prm.eval_mode = h->eval_mode;
   h->prm.limit = h->eval_mode ? h->cfg.eval_steps : h->cfg.training_steps;
+}
+
+// the scratch action / validity buffers the recorder and the request log step on
+void scratch_free(vmp_handle *h) {
+  dev_free(h->rec_act);
+  dev_free(h->rec_valid);
+  h->rec_act = nullptr;
+  h->rec_valid = nullptr;
+}
+
+// (re)start the request log of the envs flagged in env_mask (device, null = all)
+int reqlog_init(vmp_handle *h, const uint8_t *env_mask) {
+  const int64_t rows = h->rq.cap * VMP_RQ_NF;
+  const int64_t n = (int64_t)h->N * (rows > h->V ? rows : h->V);
+  const int64_t blocks = (n + 255) / 256;
+  hipLaunchKernelGGL(k_reqlog_init, dim3((unsigned)(blocks < (1 << 20) ? blocks : (1 << 20))), dim3(256),
+                     0, h->stream, h->prm, h->rq, env_mask);
+  return launched();
 }
 
 int check_policy(int32_t policy) {
@@ -266,6 +289,7 @@ int vmp_destroy(vmp_handle *h) {
   std::free(h->tr_host);
   std::free(h->tr_map);
   std::free(h->tr_info);
+  vmp_reqlog_enable(h, 0);
   vmp_record_enable(h, 0);
   delete h;
   return VMP_OK;
@@ -524,24 +548,36 @@ int vmp_reset(vmp_handle *h, const int64_t *seeds, const uint8_t *env_mask, floa
   if (!h) return fail(VMP_EINVAL, "null handle");
   dim3 grid((h->N + kWavesPerBlock - 1) / kWavesPerBlock), block(64 * kWavesPerBlock);
   hipLaunchKernelGGL(k_reset, grid, block, 0, h->stream, h->prm, seeds, env_mask, obs);
-  return launched();
+  if (const int rc = launched()) return rc;
+  return h->rq_on ? reqlog_init(h, env_mask) : VMP_OK;  // the log of the envs just reset restarts
 }
 
 // One step; with recording on, the recorder (vmp_record.hip) after it, on the
-// handle's scratch action / validity / reward where the caller passes none
+// handle's scratch action / validity / reward where the caller passes none;
+// with the request log on, its kernel (vmp_reqlog.hip) likewise
 static int step_recorded(vmp_handle *h, StepOut o) {
-  if (!h->rec_on) return launch_env(h, o);
+  if (!h->rec_on && !h->rq_on) return launch_env(h, o);
   if (!o.actions && !o.act_out) o.act_out = h->rec_act;
-  if (!o.reward) o.reward = h->rec_reward;
+  if (h->rec_on && !o.reward) o.reward = h->rec_reward;
   if (!o.valid) o.valid = h->rec_valid;
   if (const int rc = launch_env(h, o)) return rc;
-  RecArgs r = h->rec;
-  r.act = o.actions ? o.actions : o.act_out;
-  r.valid = o.valid;
-  r.reward = o.reward;
-  const size_t lds = (size_t)4 * ((h->P + 63) / 64) * sizeof(unsigned long long);
-  hipLaunchKernelGGL(k_record, dim3((h->N + 3) / 4), dim3(256), lds, h->stream, h->prm, r);
-  return launched();
+  if (h->rec_on) {
+    RecArgs r = h->rec;
+    r.act = o.actions ? o.actions : o.act_out;
+    r.valid = o.valid;
+    r.reward = o.reward;
+    const size_t lds = (size_t)4 * ((h->P + 63) / 64) * sizeof(unsigned long long);
+    hipLaunchKernelGGL(k_record, dim3((h->N + 3) / 4), dim3(256), lds, h->stream, h->prm, r);
+    if (const int rc = launched()) return rc;
+  }
+  if (h->rq_on) {
+    ReqArgs q = h->rq;
+    q.act = o.actions ? o.actions : o.act_out;
+    q.valid = o.valid;
+    hipLaunchKernelGGL(k_reqlog, dim3((h->N + 3) / 4), dim3(256), 0, h->stream, h->prm, q);
+    return launched();
+  }
+  return VMP_OK;
 }
 
 int vmp_step(vmp_handle *h, const int32_t *actions, float *obs, double *reward, uint8_t *done,
@@ -610,7 +646,7 @@ int vmp_rollout_heuristic(vmp_handle *h, int32_t policy, int32_t k_steps, double
                           int64_t *done_count) {
   if (!h || k_steps < 1) return fail(VMP_EINVAL, "null handle or k_steps < 1");
   if (const int rc = check_policy(policy)) return rc;
-  if (h->rec_on) {  // recorded: one step per launch, the recorder after each
+  if (h->rec_on || h->rq_on) {  // observed: one step per launch, the recorder / log after each
     for (int32_t k = 0; k < k_steps; k++) {
       int rc = heuristic_step_impl(h, policy, nullptr, nullptr,
                                    rewards ? rewards + (int64_t)k * h->N : nullptr, nullptr,
@@ -637,14 +673,12 @@ int vmp_record_enable(vmp_handle *h, int32_t on) {
   if (!on) {
     if (h->rec_on) (void)hipStreamSynchronize(h->stream);
     for (void *q : {(void *)h->rec.prev, (void *)h->rec.life_n, (void *)h->rec.alloc, (void *)h->rec.waits,
-                    (void *)h->rec.hist, (void *)h->rec.sums, (void *)h->rec_act, (void *)h->rec_valid,
-                    (void *)h->rec_reward})
+                    (void *)h->rec.hist, (void *)h->rec.sums, (void *)h->rec_reward})
       dev_free(q);
     std::memset(&h->rec, 0, sizeof(h->rec));
-    h->rec_act = nullptr;
-    h->rec_valid = nullptr;
     h->rec_reward = nullptr;
     h->rec_on = false;
+    if (!h->rq_on) scratch_free(h);  // the request log steps on the same scratch
     return VMP_OK;
   }
   const size_t nv = (size_t)h->N * h->V;
@@ -658,8 +692,8 @@ int vmp_record_enable(vmp_handle *h, int32_t on) {
         dev_malloc(&h->rec.waits, sizeof(uint32_t) * nv),
         dev_malloc(&h->rec.hist, sizeof(uint32_t) * (size_t)h->N * 2 * VMP_REC_BINS),
         dev_malloc(&h->rec.sums, sizeof(double) * (size_t)h->N * VMP_NREC),
-        dev_malloc(&h->rec_act, sizeof(int32_t) * nv),
-        dev_malloc(&h->rec_valid, nv),
+        h->rec_act ? hipSuccess : dev_malloc(&h->rec_act, sizeof(int32_t) * nv),
+        h->rec_valid ? hipSuccess : dev_malloc(&h->rec_valid, nv),
         dev_malloc(&h->rec_reward, sizeof(double) * (size_t)h->N)};
     for (hipError_t x : e)
       if (x != hipSuccess) {
@@ -675,6 +709,76 @@ int vmp_record_enable(vmp_handle *h, int32_t on) {
                      h->prm, h->rec);
   HIP_TRY(hipGetLastError());
   h->rec_on = true;
+  return VMP_OK;
+}
+
+// ---- per-request outcome log ----
+int vmp_reqlog_enable(vmp_handle *h, int64_t capacity) {
+  if (!h) return fail(VMP_EINVAL, "null handle");
+  if (capacity < 0) return fail(VMP_EINVAL, "vmp_reqlog_enable: capacity must be >= 0");
+  if (capacity == 0) {
+    if (h->rq_on) (void)hipStreamSynchronize(h->stream);
+    for (void *q : {(void *)h->rq.rows, (void *)h->rq.ids, (void *)h->rq.prev, (void *)h->rq.meta})
+      dev_free(q);
+    std::memset(&h->rq, 0, sizeof(h->rq));
+    h->rq_on = false;
+    if (!h->rec_on) scratch_free(h);
+    return VMP_OK;
+  }
+  ReqlogSizes sz;
+  if (const char *why = reqlog_sizes(h->N, h->V, capacity, &sz)) return fail(VMP_EINVAL, why);
+  // a new set first: on any failure the handle, and a log it had, stay as they were
+  ReqArgs q;
+  std::memset(&q, 0, sizeof(q));
+  q.cap = capacity;
+  int32_t *act_new = nullptr;
+  uint8_t *valid_new = nullptr;
+  const size_t nv = (size_t)h->N * h->V;
+  const hipError_t e[6] = {
+      dev_malloc(&q.rows, sz.rows),
+      dev_malloc(&q.ids, sz.ids),
+      dev_malloc(&q.prev, sz.prev),
+      dev_malloc(&q.meta, sz.meta),
+      h->rec_act ? hipSuccess : dev_malloc(&act_new, sizeof(int32_t) * nv),
+      h->rec_valid ? hipSuccess : dev_malloc(&valid_new, nv)};
+  for (hipError_t x : e)
+    if (x != hipSuccess) {
+      for (void *b : {(void *)q.rows, (void *)q.ids, (void *)q.prev, (void *)q.meta, (void *)act_new,
+                      (void *)valid_new})
+        dev_free(b);
+      return fail(x == hipErrorOutOfMemory ? VMP_EOOM : VMP_EDEVICE,
+                  std::string("vmp_reqlog_enable: ") + hipGetErrorString(x));
+    }
+  if (h->rq_on) {  // queued launches write the log this one replaces
+    (void)hipStreamSynchronize(h->stream);
+    for (void *b : {(void *)h->rq.rows, (void *)h->rq.ids, (void *)h->rq.prev, (void *)h->rq.meta})
+      dev_free(b);
+  }
+  h->rq = q;
+  if (act_new) h->rec_act = act_new;
+  if (valid_new) h->rec_valid = valid_new;
+  h->rq_on = true;
+  return reqlog_init(h, nullptr);
+}
+
+int vmp_reqlog_info(const vmp_handle *h, int64_t *capacity) {
+  if (!h || !capacity) return fail(VMP_EINVAL, "null argument");
+  *capacity = h->rq_on ? h->rq.cap : 0;
+  return VMP_OK;
+}
+
+int vmp_reqlog_read(vmp_handle *h, int32_t *rows, int64_t *meta) {
+  if (!h) return fail(VMP_EINVAL, "null handle");
+  if (!h->rq_on) return fail(VMP_ESTATE, "the request log is not enabled (vmp_reqlog_enable)");
+  ReqlogSizes sz;
+  if (const char *why = reqlog_sizes(h->N, h->V, h->rq.cap, &sz)) return fail(VMP_EINVAL, why);
+  if (rows) {
+    HIP_TRY(hipMemcpyAsync(rows, h->rq.rows, sz.rows, hipMemcpyDeviceToDevice, h->stream));
+    // WAIT_STEPS of the VMs waiting now is kept open on the device: closed in the copy
+    hipLaunchKernelGGL(k_reqlog_close, dim3((h->N + 3) / 4), dim3(256), 0, h->stream, h->prm, h->rq, rows);
+    if (const int rc = launched()) return rc;
+  }
+  if (meta) HIP_TRY(hipMemcpyAsync(meta, h->rq.meta, sz.meta, hipMemcpyDeviceToDevice, h->stream));
   return VMP_OK;
 }
 
@@ -852,7 +956,7 @@ int vmp_restore(vmp_handle *h, const void *src) {
   HIP_TRY(hipMemcpyAsync(h->hdr, s + l.hdr, l.nh, hipMemcpyDeviceToDevice, h->stream));
   HIP_TRY(hipMemcpyAsync(h->pm, s + l.pm, l.np, hipMemcpyDeviceToDevice, h->stream));
   HIP_TRY(hipMemcpyAsync(h->vmw, s + l.vmw, l.nv, hipMemcpyDeviceToDevice, h->stream));
-  return VMP_OK;
+  return h->rq_on ? reqlog_init(h, nullptr) : VMP_OK;  // the log is no part of a snapshot
 }
 
 int64_t vmp_debug_live_allocs(void) { return g_live.load(); }

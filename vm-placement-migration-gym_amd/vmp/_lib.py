@@ -23,7 +23,8 @@ EXPORTS = (
     "vmp_actor_head_bf16_bwd",
     "vmp_actor_head_bf16_bwd_workspace", "vmp_actor_mlp_packed_floats", "vmp_actor_mlp_pack",
     "vmp_actor_mlp_f32", "vmp_actor_mlp_head_f32", "vmp_step_mask", "vmp_record_enable",
-    "vmp_record_read", "vmp_snapshot_bytes", "vmp_snapshot", "vmp_restore",
+    "vmp_record_read", "vmp_reqlog_enable", "vmp_reqlog_info", "vmp_reqlog_read",
+    "vmp_snapshot_bytes", "vmp_snapshot", "vmp_restore",
     "vmp_debug_fail_alloc", "vmp_debug_live_allocs", "vmp_debug_stamps", "vmp_debug_occupancy",
     "vmp_debug_quiet_violations",
 )
@@ -123,6 +124,9 @@ def lib():
                                                    f32, i32, u64, u64, P, i32, P, P, P, P, P]),
         "vmp_record_enable": (ctypes.c_int, [P, i32]),
         "vmp_record_read": (ctypes.c_int, [P, P, P]),
+        "vmp_reqlog_enable": (ctypes.c_int, [P, i64]),
+        "vmp_reqlog_info": (ctypes.c_int, [P, P]),
+        "vmp_reqlog_read": (ctypes.c_int, [P, P, P]),
         "vmp_snapshot_bytes": (ctypes.c_int, [P, P]),
         "vmp_snapshot": (ctypes.c_int, [P, P]),
         "vmp_restore": (ctypes.c_int, [P, P]),
@@ -139,7 +143,7 @@ def lib():
         if f is None:
             raise VmpError(f"libvmp lacks {name}")
         f.restype, f.argtypes = res, args
-    if L.vmp_abi_version() != 13:
+    if L.vmp_abi_version() != 14:
         raise VmpError("libvmp ABI mismatch")
     _lib = L
     return L

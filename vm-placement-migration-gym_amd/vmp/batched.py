@@ -341,6 +341,43 @@ class BatchedVmEnv:
         return [summary_from_device(hist[i], sums[i], ctr[i], st[i], self.P)
                 for i in range(self.n_envs)]
 
+    # ------------------------------------------- per-request outcome log
+    def request_log(self, on=True, capacity=None):
+        """Start (on=True) or free the per-request outcome log of every env on
+        the device (vmp_reqlog_enable): one row per request offered since the
+        env's last reset, updated after every step (see vmp.reqlog). capacity:
+        rows per env; a traced env defaults to the largest request count among
+        the traces its envs replay, an RNG env must pass one. The log starts
+        from the current state (call it right after reset); reset() restarts
+        the log of the envs it resets. Not during graph capture; a graph
+        captured before the call does not log."""
+        h = self._bind()
+        if not on:
+            check(lib().vmp_reqlog_enable(h, 0))
+            return
+        if capacity is None:
+            info = self.trace_info()
+            if info is None:
+                raise ValueError("request_log needs a capacity on an env without a trace")
+            capacity = max(1, int(info["requests"][np.unique(info["trace_of_env"])].max()))
+        if int(capacity) < 1:
+            raise ValueError("capacity must be >= 1")
+        with torch.cuda.device(self.device):
+            check(lib().vmp_reqlog_enable(h, int(capacity)))
+
+    def request_log_read(self):
+        """The log so far as a `vmp.reqlog.RequestLog` (non-destructive)."""
+        from .reqlog import NF, RequestLog
+        h = self._bind()
+        cap = ctypes.c_int64()
+        check(lib().vmp_reqlog_info(h, ctypes.byref(cap)))
+        if cap.value == 0:
+            raise VmpError("the request log is not enabled (request_log())")
+        rows = self._empty((self.n_envs, cap.value, NF), torch.int32)
+        meta = self._empty((self.n_envs, 3), torch.int64)
+        check(lib().vmp_reqlog_read(h, ptr(rows), ptr(meta)))
+        return RequestLog(rows.cpu().numpy(), meta.cpu().numpy())
+
     def rank(self):
         h = self._bind()
         r = self._empty((self.n_envs,), torch.int64)

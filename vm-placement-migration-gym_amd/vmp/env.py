@@ -75,6 +75,15 @@ class VmEnv(_GymEnv):
         else:
             self._b.set_trace(trace)
 
+    def request_log(self, on=True, capacity=None):
+        """Per-request outcome log of this env (BatchedVmEnv.request_log)."""
+        self._b.request_log(on, capacity)
+
+    def request_log_read(self):
+        """The log so far: a vmp.reqlog.RequestLog of one env, trimmed to the
+        requests observed."""
+        return self._b.request_log_read().env(0)
+
     # ------------------------------------------------------- state views
     def _st(self):
         return {k: v[0].cpu().numpy() for k, v in self._b.state().items()}

@@ -14,6 +14,7 @@ comes back to the host. This replaces the reference's process fan-out
     python -m vmp.exp reward --agents ppo --weights 'w/ppo-{reward}.pt'   # exp_reward.py
     python -m vmp.exp migration_ratio --agents bestfit,ppo --weights 'w/ppo-{reward}.pt'
     python -m vmp.exp paired --trace a.npz,b.npz           # every agent on the same requests
+    python -m vmp.exp paired --trace a.npz --requests r.csv   # ... and what became of each request
 
 Rows are printed in exp_suspension.py's CSV layout (exp_suspension.py:51-58):
 Agent, Load, Service Length, Total Served, Valid Suspend Actions, Valid
@@ -236,11 +237,17 @@ def paired_sweep(traces, agents=("firstfit", "bestfit"), config=None, eval_steps
     (default: the longest trace). A traced env's requests do not depend on what
     the policy did with the earlier ones, so the rows of one trace compare the
     agents on one workload. One CSV row per (agent, trace), see PAIRED_HEADER."""
+    return _paired_run(traces, agents, config, eval_steps, weights, device, False)[0]
+
+
+def _paired_run(traces, agents, config, eval_steps, weights, device, log):
+    """paired_sweep's runs; log=True: with the per-request outcome log on.
+    Returns (rows, {agent: RequestLog})."""
     traces = list(traces)
     cfg = dict(ENV100, reward_function="wr") if config is None else dict(config)
     steps = int(eval_steps) if eval_steps is not None else max(t.steps for t in traces)
     cfg["eval_steps"] = max(int(cfg.get("eval_steps", 0)), steps)
-    rows = []
+    rows, logs = [], {}
     for name in agents:
         if name != "ppo" and name not in HEURISTICS:
             raise ValueError(f"agent {name!r} has no batched GPU path")
@@ -249,6 +256,8 @@ def paired_sweep(traces, agents=("firstfit", "bestfit"), config=None, eval_steps
         env.eval(True)
         env.reset()
         env.record(True)
+        if log:  # before the capture below: a graph captured earlier would not log
+            env.request_log(True)
         if name == "ppo":
             from .ppo import ActStepGraph, PPOAgent, PPOConfig
             ag = PPOAgent(env, PPOConfig(**PPO100))
@@ -260,8 +269,75 @@ def paired_sweep(traces, agents=("firstfit", "bestfit"), config=None, eval_steps
         else:
             env.rollout(name, steps)
         summ = env.record_summary()
+        if log:
+            logs[name] = env.request_log_read()
         env.close()
         rows += [paired_row(name, i, t, s) for i, (t, s) in enumerate(zip(traces, summ))]
+    return rows, logs
+
+
+def paired_requests_header(agents):
+    return "Trace, Request, Arrival Step, CPU, Memory, Runtime" + "".join(
+        ", %s Slot, %s Placed, %s Finished, %s Suspends, %s Wait Steps" % ((a,) * 5)
+        for a in agents)
+
+
+def paired_requests(traces, agents=("firstfit", "bestfit"), config=None, eval_steps=None,
+                    weights=None, device="cuda:0", logs=None):
+    """What became of every request under every agent: paired_sweep's runs with
+    the per-request outcome log on (BatchedVmEnv.request_log), one CSV row per
+    (trace, request) in paired_requests_header's layout: the trace's arrival
+    step, cpu, mem (hundredths) and runtime of the request, then per agent its
+    slot status (-2 not observed, -1 dropped, else the slot), the timesteps of
+    its first placement and of its finish (0 = not yet), its valid suspensions
+    and its waiting steps. logs ({agent: RequestLog} of earlier runs on these
+    traces, env i = trace i): format those, run nothing."""
+    traces = list(traces)
+    if logs is None:
+        logs = _paired_run(traces, agents, config, eval_steps, weights, device, True)[1]
+    rows = []
+    for i, t in enumerate(traces):
+        step_of = np.repeat(np.arange(t.steps), t.arrivals())
+        for j in range(t.requests):
+            row = "%d,%d,%d,%d,%d,%d" % (i, j, step_of[j], t.cpu[j], t.mem[j], t.runtime[j])
+            for a in agents:
+                lg = logs[a]
+                r = lg.rows[i, j] if j < lg.capacity else (-2, 0, 0, 0, 0, 0)
+                row += ",%d,%d,%d,%d,%d" % (r[0], r[2], r[3], r[4], r[5])
+            rows.append(row)
+    return rows
+
+
+PAIRED_DIFF_HEADER = ("Trace, Agent A, Agent B, Placed Both, Mean Pending Difference, "
+                      "Median Pending Difference, Dropped Only A, Dropped Only B, Finished Both, "
+                      "Mean Sojourn Difference")
+
+
+def paired_differences(traces, agents, logs):
+    """Per trace and pair of agents (A before B in `agents`), over the requests
+    of the trace: how many were placed under both and the mean and median of
+    pending_steps(A) - pending_steps(B) over those; the requests dropped under
+    A only and under B only; how many finished under both and the mean of
+    sojourn(A) - sojourn(B) over those. One CSV row each (PAIRED_DIFF_HEADER);
+    a mean over no request prints nan."""
+    fmt = lambda x: "%.3f" % x if x == x else "nan"  # noqa: E731
+    rows = []
+    for i, t in enumerate(traces):
+        for x in range(len(agents)):
+            for y in range(x + 1, len(agents)):
+                la, lb = logs[agents[x]], logs[agents[y]]
+                n = min(t.requests, la.capacity, lb.capacity)
+                both = la.is_placed[i, :n] & lb.is_placed[i, :n]
+                d = (la.pending_steps[i, :n] - lb.pending_steps[i, :n])[both].astype(np.float64)
+                fin = la.is_finished[i, :n] & lb.is_finished[i, :n]
+                sj = (la.sojourn[i, :n] - lb.sojourn[i, :n])[fin].astype(np.float64)
+                rows.append("%d,%s,%s,%d,%s,%s,%d,%d,%d,%s" % (
+                    i, agents[x], agents[y], int(both.sum()),
+                    fmt(d.mean() if d.size else float("nan")),
+                    fmt(float(np.median(d)) if d.size else float("nan")),
+                    int((la.dropped[i, :n] & ~lb.dropped[i, :n]).sum()),
+                    int((lb.dropped[i, :n] & ~la.dropped[i, :n]).sum()), int(fin.sum()),
+                    fmt(sj.mean() if sj.size else float("nan"))))
     return rows
 
 
@@ -435,6 +511,9 @@ def main(argv=None):
     ap.add_argument("--trace", default=None, help="paired: comma list of Trace .npz files")
     ap.add_argument("--config", default=None,
                     help="paired: YAML with an `environment:` section (default config/100.yml's, wr)")
+    ap.add_argument("--requests", default=None,
+                    help="paired: also write one row per (trace, request) to this CSV and print "
+                         "the per-request paired differences")
     ap.add_argument("--out", default=None)
     a = ap.parse_args(argv)
     agents = a.agents.split(",")
@@ -452,8 +531,14 @@ def main(argv=None):
             if a.reward:
                 cfg["reward_function"] = a.reward
         header = PAIRED_HEADER
-        rows = paired_sweep([Trace.load(p) for p in a.trace.split(",")], agents=agents, config=cfg,
-                            eval_steps=a.eval_steps, weights=a.weights)
+        traces = [Trace.load(p) for p in a.trace.split(",")]
+        rows, logs = _paired_run(traces, agents, cfg, a.eval_steps, a.weights, "cuda:0",
+                                 a.requests is not None)
+        if a.requests is not None:
+            with open(a.requests, "w") as f:
+                f.write("\n".join([paired_requests_header(agents)]
+                                  + paired_requests(traces, agents, logs=logs)) + "\n")
+            rows = rows + [PAIRED_DIFF_HEADER] + paired_differences(traces, agents, logs)
     elif a.experiment == "suspension":
         header = SUSPENSION_HEADER
         rows = suspension_sweep(
