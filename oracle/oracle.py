@@ -69,8 +69,10 @@ def lib():
             "oracle_pcg_double": (None, [u64, i64, P]),
             "oracle_pcg_around": (None, [u64, i64, dbl, dbl, P]),
             "oracle_pcg_poisson": (u64, [u64, dbl, i64, P]),
+            "oracle_pcg_poisson_at": (u64, [u64, u64, dbl, i64, P, P]),
             "oracle_pcg_advance_raw": (u64, [u64, u64]),
-            "oracle_pw_sum": (dbl, [P, i64]), "oracle_argsort_f32": (None, [P, i64, P]),
+            "oracle_pw_sum": (dbl, [P, i64]), "oracle_mean_var": (None, [P, i64, P, P]),
+            "oracle_argsort_f32": (None, [P, i64, P]),
             "oracle_rollout": (i64, [P, i32, i64, i64, i64, i32, i32, i32, P, P]),
             "oracle_rollout_timed": (None, [P, i32, i64, i64, i64, i64, i32, i32, i32, i32, P, P]),
         }

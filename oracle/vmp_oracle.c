@@ -210,7 +210,21 @@ static double pw_sum(const double *a, int64_t n) {
     return pw_sum(a, n2) + pw_sum(a + n2, n - n2);
   }
 }
-static double np_sum(const double *a, int64_t n) { return 0.0 + pw_sum(a, n); }
+/* add.reduce over a contiguous array runs its inner loop once per iterator
+ * buffer of NPY_BUFSIZE = 8192 elements: the result starts at the identity 0.0
+ * and takes pw_sum of each buffer in order, so the pairwise recursion never
+ * spans more than 8192 elements. */
+#define NP_BUFSIZE 8192
+static double np_sum(const double *a, int64_t n) {
+  double res = 0.0;
+  int64_t o = 0;
+  do {
+    const int64_t m = n - o < NP_BUFSIZE ? n - o : NP_BUFSIZE;
+    res += pw_sum(a + o, m);
+    o += m;
+  } while (o < n);
+  return res;
+}
 static double np_mean(const double *a, int64_t n) { return np_sum(a, n) / (double)n; }
 /* _methods._var with ddof=0: mean, (x-mean)**2 elementwise, sum, / n. */
 static double np_var(const double *a, int64_t n, double *tmp) {
@@ -718,6 +732,20 @@ uint64_t oracle_pcg_poisson(uint64_t seed, double lam, int64_t n, int64_t *out) 
   for (int64_t i = 0; i < n; i++) out[i] = poisson(&r, lam);
   return pcg_next64(&r);
 }
+/* The same from `offset` raw draws into the stream, with the 128-bit state
+ * (hi, lo) after every draw. */
+uint64_t oracle_pcg_poisson_at(uint64_t seed, uint64_t offset, double lam, int64_t n, int64_t *out,
+                               uint64_t *states) {
+  pcg64 r;
+  pcg_seed(&r, seed);
+  pcg_advance(&r, offset);
+  for (int64_t i = 0; i < n; i++) {
+    out[i] = poisson(&r, lam);
+    states[2 * i] = (uint64_t)(r.state >> 64);
+    states[2 * i + 1] = (uint64_t)r.state;
+  }
+  return pcg_next64(&r);
+}
 uint64_t oracle_pcg_advance_raw(uint64_t seed, uint64_t delta) {
   pcg64 r;
   pcg_seed(&r, seed);
@@ -725,6 +753,11 @@ uint64_t oracle_pcg_advance_raw(uint64_t seed, uint64_t delta) {
   return pcg_next64(&r);
 }
 double oracle_pw_sum(const double *a, int64_t n) { return np_sum(a, n); }
+/* np.mean and np.var of a (tmp: n doubles of scratch). */
+void oracle_mean_var(const double *a, int64_t n, double *tmp, double out[2]) {
+  out[0] = np_mean(a, n);
+  out[1] = np_var(a, n, tmp);
+}
 void oracle_argsort_f32(const float *v, int64_t n, int64_t *out) {
   for (int64_t i = 0; i < n; i++) out[i] = i;
   aquicksort_f32(v, out, n);

@@ -296,6 +296,54 @@ def test_large_v_block_kernel_vs_oracle(policy, reward):
         b.close()
 
 
+def test_sums_past_one_numpy_buffer_vs_oracle():
+    """More than 8192 summands: numpy's add.reduce sums pairwise per buffer of
+    8192 elements and adds the buffers in order, so above that size the order
+    of additions is not one recursion over n. P200 / V10240 at lambda 9500:
+    the first step accepts more than 8192 requests (the sums of the accepted
+    sizes) and more than 8192 VMs exist from then on (the target means and
+    variances of the kl reward; the means are left uncapped so that stats()
+    shows them), both asserted on the oracle's side; rewards, counters,
+    stats() and the state against the oracle."""
+    from vmp.batched import BatchedVmEnv
+    P, V = 200, 10240
+    cfg = dict(pms=P, vms=V, arrival_rate=9500.0, service_length=50, training_steps=10000,
+               eval_steps=100000, seed=4, reward_function="kl", sequence="uniform",
+               cap_target_util=False, beta=0.5, allow_null_action=True)
+    seeds = np.array([4, 5], dtype=np.int64)
+    b = BatchedVmEnv(_cfg(cfg), 2, seeds=seeds, device=DEV)
+    b.eval(True)
+    orc = [O.OracleEnv(dict(cfg, seed=int(s))) for s in seeds]
+    for e, s in zip(orc, seeds):
+        e.eval(True)
+        e.reset(int(s))
+    most_existing, most_accepted = 0, 0
+    for t in range(6):
+        _, rew, _, _, act = b.heuristic_step("firstfit", want_actions=True)
+        rew, act = rew.cpu().numpy(), act.cpu().numpy()
+        stats = b.stats().cpu().numpy()
+        ctr = b.counters().cpu().numpy()
+        for i, e in enumerate(orc):
+            c0 = e.counters()[0]
+            a = e.firstfit()
+            assert np.array_equal(a, act[i]), (t, i)
+            _, r, _, _ = e.step(a)
+            c1, misc = e.counters()
+            most_accepted = max(most_accepted, int((c1[0] - c0[0]) - (c1[4] - c0[4])))
+            most_existing = max(most_existing, int((e.state()[0] <= P).sum()))
+            assert T.kl_close(rew[i], r), (t, i, rew[i], r)
+            assert np.array_equal(ctr[i], c1), (t, i, ctr[i], c1)
+            assert np.array_equal(stats[i], misc), (t, i, stats[i], misc)
+    assert most_existing > 8192 and most_accepted > 8192, (most_existing, most_accepted)
+    sd = b.state()
+    for i, e in enumerate(orc):
+        so = e.state()
+        for k, name in enumerate(("vm_placement", "vm_cpu", "vm_memory", "cpu", "memory",
+                                  "vm_remaining_runtime")):
+            assert np.array_equal(sd[name][i].cpu().numpy(), so[k]), (name, i)
+    b.close()
+
+
 def test_c5_steady_state_bestfit_kl_vs_oracle():
     """BASELINE config 5 (P1000 / V10000, lambda = 1000/0.55/1000,
     L = 1000, reward kl, BestFit) from reset through the 2·L-step fill into the

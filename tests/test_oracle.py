@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from oracle import oracle as O
+from tests import prims_cases as C
 from tests import traj as T
 from tests.golden_hash import obs_hash, state_hash
 
@@ -51,10 +52,41 @@ def test_advance_matches_stepping():
 
 
 def test_pairwise_sum_matches_numpy():
+    """np.sum of a contiguous float64 array, bit for bit, through every plan
+    border of the device's sum and across numpy's reduction buffer of 8192
+    elements (pairwise per buffer, the buffers added in order), for summands
+    whose order of addition shows (tests/prims_cases.py)."""
     rng = np.random.default_rng(3)
     for n in list(range(0, 40)) + [127, 128, 129, 255, 256, 300, 1000, 1037, 4099]:
         a = np.around(rng.uniform(0.1, 1, n), 2)
         assert O.lib().oracle_pw_sum(O._p(a), n) == np.sum(a), n
+    bad = []
+    for fam in C.PW_FAMILIES:
+        pool = C.pw_values(fam)
+        for off, n in C.pw_cases():
+            a = np.ascontiguousarray(pool[off:off + n])
+            got, exp = O.lib().oracle_pw_sum(O._p(a), n), float(np.sum(a))
+            if np.float64(got).view(np.uint64) != np.float64(exp).view(np.uint64):
+                bad.append((fam, off, n, got, exp))
+    assert not bad, (len(bad), bad[:8])
+
+
+def test_mean_var_match_numpy_past_one_buffer():
+    """The oracle's np_mean / np_var (the kl reward's moments of the existing
+    VMs) against np.mean / np.var at more than 8192 elements."""
+    bad = []
+    for fam in C.PW_FAMILIES:
+        pool = C.pw_values(fam)
+        for off, n in C.pw_cases():
+            if n < 8184:
+                continue
+            a = np.ascontiguousarray(pool[off:off + n])
+            tmp, out = np.zeros(n), np.zeros(2)
+            O.lib().oracle_mean_var(O._p(a), n, O._p(tmp), O._p(out))
+            exp = np.array([np.mean(a), np.var(a)])
+            if not np.array_equal(out.view(np.uint64), exp.view(np.uint64)):
+                bad.append((fam, off, n, out.tolist(), exp.tolist()))
+    assert not bad, (len(bad), bad[:8])
 
 
 def test_argsort_is_a_permutation_sorting_keys():

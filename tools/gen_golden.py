@@ -223,6 +223,15 @@ def gen_trajs():
                                seed=23, eval_steps=400), "bf", 400)
 
 
+def gen_traj_big():
+    """More than 8192 summands in the reference's own sums (numpy reduces in
+    buffers of 8192 elements): P200 / V10240 at lambda 9500 accepts more than
+    8192 requests in the first step and holds more than 8192 VMs from then on."""
+    run_traj("p200v10240_ff", cfg(pms=200, vms=10240, arrival_rate=9500.0, service_length=50,
+                                  seed=4, eval_steps=100, cap_target_util=False), "ff", 8,
+             p_susp=0.002, p_rand=0.001)
+
+
 def load_ref_weights():
     sd = torch.load(os.path.join(REF, "weights-10", "ppo-wr.pt"), map_location="cpu",
                     weights_only=True)
@@ -446,7 +455,9 @@ def gen_ppo100_steps():
 
 
 if __name__ == "__main__":
-    what = sys.argv[1:] or ["rng", "traj", "ppo", "ppo100"]
+    what = sys.argv[1:] or ["rng", "traj", "traj_big", "ppo", "ppo100"]
+    if "traj_big" in what:
+        gen_traj_big()
     if "ppo100" in what:
         gen_ppo100()
     if "ppo100" in what or "ppo100_steps" in what:

@@ -223,17 +223,8 @@ static int create_rest(vmp_handle *h, const vmp_config *cfg, int32_t n_env, cons
     HIP_TRY(hipMemcpy(h->pois_dev, pc, sizeof(pc), hipMemcpyHostToDevice));
     p.pois = h->pois_dev;
     // PCG64 jump table for the lane-parallel draws (k_env prologue)
-    uint64_t jt[64 * 4];
-    const unsigned __int128 a = ((unsigned __int128)0x2360ED051FC65DA4ULL << 64) | 0x4385DF649FCCF645ULL;
-    unsigned __int128 A = a, M = 1;
-    for (int j = 0; j < 64; j++) {
-      jt[4 * j + 0] = (uint64_t)(A >> 64);
-      jt[4 * j + 1] = (uint64_t)A;
-      jt[4 * j + 2] = (uint64_t)(M >> 64);
-      jt[4 * j + 3] = (uint64_t)M;
-      A *= a;
-      M = M * a + 1;
-    }
+    uint64_t jt[kJumpWords];
+    pcg_jump_table(jt);
     HIP_TRY(dev_malloc(&h->jump_dev, sizeof(jt)));
     HIP_TRY(hipMemcpy(h->jump_dev, jt, sizeof(jt), hipMemcpyHostToDevice));
     p.jump = h->jump_dev;

@@ -1,6 +1,7 @@
-// vmp_host.h — host-side plumbing of the C ABI (vmp_capi.cpp alone includes
-// it): the thread's error text, the counted device allocations, and the
-// per-config Poisson setup, evaluated with glibc exactly as numpy's C code does.
+// vmp_host.h — host-side plumbing of the C ABI (vmp_capi.cpp, and the
+// test-only wrappers of vmp_prims.hip): the thread's error text, the counted
+// device allocations, the PCG64 jump table, and the per-config Poisson setup,
+// evaluated with glibc exactly as numpy's C code does.
 #ifndef VMP_HOST_H
 #define VMP_HOST_H
 
@@ -68,6 +69,24 @@ inline void dev_free(void *p) {
   if (!p) return;
   (void)hipFree(p);
   g_live--;
+}
+
+// PCG64 jump table of the lane-parallel draws (ParRng, vmp_env_common.h):
+// entry j holds (A_j, M_j), each as (hi, lo), with the state after j + 1 draws
+// s_j = A_j * base + M_j * inc, i.e. A_j = a^(j+1), M_j = a^j + ... + a + 1
+// for the LCG multiplier a.
+constexpr int kJumpWords = 64 * 4;
+inline void pcg_jump_table(uint64_t jt[kJumpWords]) {
+  const unsigned __int128 a = ((unsigned __int128)0x2360ED051FC65DA4ULL << 64) | 0x4385DF649FCCF645ULL;
+  unsigned __int128 A = a, M = 1;
+  for (int j = 0; j < 64; j++) {
+    jt[4 * j + 0] = (uint64_t)(A >> 64);
+    jt[4 * j + 1] = (uint64_t)A;
+    jt[4 * j + 2] = (uint64_t)(M >> 64);
+    jt[4 * j + 3] = (uint64_t)M;
+    A *= a;
+    M = M * a + 1;
+  }
 }
 
 // random_loggam (numpy distributions.c), host copy for the PTRS table.

@@ -308,6 +308,13 @@ __device__ __noinline__ void wave_aquicksort(KV v, uint16_t LDSP *t, int num,
 // instead of sorting the block (~e log e more partitions). The stack holds
 // the pending lower parts of one path: at most 2 log2(n) + 1 entries (the
 // depth limit ends a path in heapsort). Returns the position, or -1.
+//
+// The depth limit: numpy tests cdepth < 0 only on a part it pops, i.e. the
+// LARGER part of its partition; the smaller part, which it goes on with, is
+// partitioned whatever its depth. Which part this walk goes on with is not
+// numpy's choice, so every part carries that bit (`cont`: numpy goes on with
+// it, no depth test; bit 0 of its depth entry while it waits), and a part is
+// heapsorted exactly where numpy heapsorts it.
 template <class KV, class Fit>
 __device__ __noinline__ int wave_aqselect_top(KV v, uint16_t LDSP *t, int num,
                                               int32_t LDSP *stack, int lo, int hi,
@@ -330,9 +337,10 @@ __device__ __noinline__ int wave_aqselect_top(KV v, uint16_t LDSP *t, int num,
     return -1;
   };
   int found = -1;
+  bool cont = false;
   for (;;) {
     if (pr < lo || pl > hi) goto stack_pop;
-    if (cdepth < 0) {
+    if (cdepth < 0 && !cont) {
       if (lane == 0) aheapsort_lds(v, t + pl, pr - pl + 1);
       wsync();
       found = scan(pl, pr);
@@ -341,18 +349,22 @@ __device__ __noinline__ int wave_aqselect_top(KV v, uint16_t LDSP *t, int num,
     }
     while ((pr - pl) > 15) {
       const int pi = wave_partition(v, t, pl, pr, scr);
+      const bool lower_small = pi - pl < pr - pi;  // numpy goes on with the lower part
+      --cdepth;
       if (lane == 0) {  // the lower part waits; the upper part goes on
         stack[sp] = pl;
         stack[sp + 1] = pi - 1;
+        depth[dp] = cdepth * 2 + (lower_small ? 1 : 0);
       }
       sp += 2;
-      pl = pi + 1;
-      --cdepth;
-      if (lane == 0) depth[dp] = cdepth;
       dp++;
+      pl = pi + 1;
+      cont = !lower_small;
       wsync();
       if (pr < lo || pl > hi) goto stack_pop;
+      if (!cont && cdepth < 0) break;  // numpy pops this part: heapsort
     }
+    if (!cont && cdepth < 0) continue;  // of any size, as numpy's test after a pop
     wave_leaf_sort(v, t, pl, pr);
     found = scan(pl, pr);
     if (found >= 0) break;
@@ -362,7 +374,11 @@ __device__ __noinline__ int wave_aqselect_top(KV v, uint16_t LDSP *t, int num,
     sp -= 2;
     pl = stack[sp];
     pr = stack[sp + 1];
-    cdepth = depth[--dp];
+    {
+      const int d = depth[--dp];
+      cdepth = d >> 1;
+      cont = (d & 1) != 0;
+    }
     // the popped range is the lower part of a partition whose pivot sits at
     // pr + 1, settled, and every position above it has been checked
     if (pr + 1 >= lo && pr + 1 <= hi && fit((int)t[pr + 1])) {

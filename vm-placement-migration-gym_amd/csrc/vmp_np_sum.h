@@ -25,60 +25,76 @@ struct PwLds {
   double LDSP *val;             // leaf sums, + value stack
 };
 
-// lane 0 only: leaves of the recursion for n, left to right.
-__device__ __forceinline__ int pw_plan(int n, const PwLds &S) {
-  int sp = 0, nl = 0;
-  S.stk[0] = 0;
-  S.stk[1] = n;
-  sp = 2;
-  while (sp > 0) {
-    sp -= 2;
-    const int o = S.stk[sp], m = S.stk[sp + 1];
-    if (m <= 128) {
-      S.lo[nl] = o;
-      S.len[nl] = m;
-      nl++;
-    } else {
-      int n2 = m / 2;
-      n2 -= n2 % 8;
-      S.stk[sp] = o + n2;  // right, popped second
-      S.stk[sp + 1] = m - n2;
-      S.stk[sp + 2] = o;   // left, popped first
-      S.stk[sp + 3] = n2;
-      sp += 4;
+// numpy's add.reduce hands DOUBLE_pairwise_sum one iterator buffer at a time
+// (NPY_BUFSIZE = 8192 elements of a contiguous array): the result is
+// 0.0 + pw(a[0:8192]) + pw(a[8192:16384]) + ..., the buffers added in order.
+// One buffer (n <= 8192) is the plain recursion over n.
+constexpr int kNpBufSize = 8192;
+
+// lane 0 only: leaves of the recursions for n, left to right (buffer by buffer).
+// Out of line, as pw_combine: the LDS plan is the rare path of the wave
+// kernels, and inlined its loops cost the common path registers.
+__device__ __noinline__ int pw_plan(int n, PwLds S) {
+  int nl = 0;
+  for (int base = 0; base < n; base += kNpBufSize) {
+    int sp = 2;
+    S.stk[0] = base;
+    S.stk[1] = n - base < kNpBufSize ? n - base : kNpBufSize;
+    while (sp > 0) {
+      sp -= 2;
+      const int o = S.stk[sp], m = S.stk[sp + 1];
+      if (m <= 128) {
+        S.lo[nl] = o;
+        S.len[nl] = m;
+        nl++;
+      } else {
+        int n2 = m / 2;
+        n2 -= n2 % 8;
+        S.stk[sp] = o + n2;  // right, popped second
+        S.stk[sp + 1] = m - n2;
+        S.stk[sp + 2] = o;   // left, popped first
+        S.stk[sp + 3] = n2;
+        sp += 4;
+      }
     }
   }
   return nl;
 }
 
-// lane 0 only: pw(n) = pw(n2) + pw(n - n2) over the leaf sums in val[].
-__device__ __forceinline__ double pw_combine(int n, const PwLds &S, int nl) {
+// lane 0 only: per buffer, pw(m) = pw(n2) + pw(m - n2) over the leaf sums in
+// val[]; the buffers' sums are added in order onto 0.0 (one buffer: its sum).
+__device__ __noinline__ double pw_combine(int n, PwLds S, int nl) {
   double LDSP *vs = S.val + nl;  // value stack after the leaf sums
-  int sp = 0, vsp = 0, leaf = 0;
-  S.stk[0] = n;
-  S.stk[1] = 0;
-  sp = 2;
-  while (sp > 0) {
-    sp -= 2;
-    const int m = S.stk[sp], ph = S.stk[sp + 1];
-    if (m <= 128) {
-      vs[vsp++] = S.val[leaf++];
-    } else if (ph == 0) {
-      int n2 = m / 2;
-      n2 -= n2 % 8;
-      S.stk[sp + 1] = 1;  // revisit after both children
-      S.stk[sp + 2] = m - n2;
-      S.stk[sp + 3] = 0;
-      S.stk[sp + 4] = n2;
-      S.stk[sp + 5] = 0;
-      sp += 6;
-    } else {
-      const double b = vs[--vsp];
-      const double a = vs[--vsp];
-      vs[vsp++] = a + b;
+  int leaf = 0;
+  double acc = 0.0;
+  for (int base = 0; base < n; base += kNpBufSize) {
+    int sp = 2, vsp = 0;
+    S.stk[0] = n - base < kNpBufSize ? n - base : kNpBufSize;
+    S.stk[1] = 0;
+    while (sp > 0) {
+      sp -= 2;
+      const int m = S.stk[sp], ph = S.stk[sp + 1];
+      if (m <= 128) {
+        vs[vsp++] = S.val[leaf++];
+      } else if (ph == 0) {
+        int n2 = m / 2;
+        n2 -= n2 % 8;
+        S.stk[sp + 1] = 1;  // revisit after both children
+        S.stk[sp + 2] = m - n2;
+        S.stk[sp + 3] = 0;
+        S.stk[sp + 4] = n2;
+        S.stk[sp + 5] = 0;
+        sp += 6;
+      } else {
+        const double b = vs[--vsp];
+        const double a = vs[--vsp];
+        vs[vsp++] = a + b;
+      }
     }
+    if (n <= kNpBufSize) return vs[0];
+    acc += vs[0];
   }
-  return vs[0];
+  return acc;
 }
 
 __device__ __forceinline__ double readlane_f64(double x, int l) {
@@ -189,7 +205,8 @@ __device__ __forceinline__ double wave_pw_sum(int n, F f, const PwLds &S) {
     int cnt = 0;
     return pw_comb_r<RD>(n, cnt, myval);
   }
-  // deeper recursion (n > pw_reg_cap(RD), P-sized sums of big configs): LDS plan
+  // deeper recursion (n > pw_reg_cap(RD), P-sized sums of big configs): LDS
+  // plan, which also splits n > kNpBufSize into numpy's buffers
   int nl = 1;
   if (lane == 0) S.stk[kPwStackWords - 1] = pw_plan(n, S);
   wsync();
