@@ -85,6 +85,34 @@ extern "C" {
 #define VMP_RQ_NEXT 1       /* total_requests now: the ids observed are [FIRST, NEXT) */
 #define VMP_RQ_LOST 2       /* requests whose id was >= capacity: not logged */
 #define VMP_RQ_NMETA 3
+/* per-step time series (vmp_series_read): one f64[VMP_SR_NF] row per window of `stride` steps.
+ * Fields 1..12 are sums over the window's steps (divide by STEPS for the window mean), fields
+ * 13..18 the env's int64 counters after the window's last step, stored as f64: exact below 2^53 */
+#define VMP_SR_STEPS 0            /* steps folded into the row; 0 = never written */
+#define VMP_SR_REWARD 1           /* the step's reward */
+#define VMP_SR_WAITING_RATIO 2    /* waiting_ratio (VMP_ST_WAITING_RATIO) */
+#define VMP_SR_CPU_SUM 3          /* np.sum(cpu) over the PMs, numpy's pairwise order */
+#define VMP_SR_MEM_SUM 4          /* np.sum(memory) */
+#define VMP_SR_CPU_VAR 5          /* np.var(cpu): two-pass, the mean from the pairwise sum */
+#define VMP_SR_MEM_VAR 6          /* np.var(memory) */
+#define VMP_SR_TARGET_CPU_MEAN 7  /* env.py:116-121 with cap_target_util applied */
+#define VMP_SR_TARGET_MEM_MEAN 8
+#define VMP_SR_USED_PM 9          /* _get_rank: PMs hosting at least one VM */
+#define VMP_SR_EMPTY_PM 10        /* P - count_nonzero(cpu): base.py:134's `used_pm` */
+#define VMP_SR_WAITING 11         /* slots with placement == WAIT */
+#define VMP_SR_RUNNING 12         /* slots with placement < P */
+#define VMP_SR_TIMESTEP 13        /* ... and the counters, as vmp_get_counters returns them */
+#define VMP_SR_TOTAL_REQUESTS 14
+#define VMP_SR_SERVED 15
+#define VMP_SR_SUSPEND 16
+#define VMP_SR_PLACE 17
+#define VMP_SR_DROPPED 18
+#define VMP_SR_NF 19
+/* ... and its per-env meta, int64[VMP_SR_NMETA] */
+#define VMP_SR_FIRST 0      /* the env's timestep when its series started */
+#define VMP_SR_COUNT 1      /* steps observed since then: the next step folds into row COUNT / stride */
+#define VMP_SR_LOST 2       /* steps whose row index was >= capacity: counted, not stored */
+#define VMP_SR_NMETA 3
 /* actor-head modes (vmp_policy_head) */
 #define VMP_HEAD_SAMPLE 0 /* Network.get_action(obs, action=None, mask) (ppo.py:115-126) */
 #define VMP_HEAD_GIVEN 1  /* Network.get_action(obs, action, mask): log_prob/entropy only */
@@ -502,6 +530,45 @@ int vmp_reqlog_info(const vmp_handle *h, int64_t *capacity);
  * open count, written at events only; the read closes it in the caller's copy with one small
  * kernel, so the rows read are always the counts up to the last step.) */
 int vmp_reqlog_read(vmp_handle *h, int32_t *rows, int64_t *meta);
+
+/* Per-step time series on the device: how reward, waiting ratio, PM utilisation, target means,
+ * used PMs and the counters develop over the steps of every env (the per-step lists of the
+ * reference's Record, src/record.py:13-32), without a host copy per step. A third observer
+ * behind the step, beside the recorder and the request log: one more kernel after every
+ * vmp_step / vmp_step_mask / vmp_heuristic_step (vmp_rollout_heuristic runs one step per launch
+ * while it is on) reads the post-step state and the step's reward and changes no env state.
+ * Per env the series holds `capacity` rows f64[VMP_SR_NF]; row r covers the observed steps
+ * [r stride, (r + 1) stride) counted from the env's series start. The first step of a window
+ * stores fields 0..12, each later step adds its values to them with one f64 add in step order
+ * (at stride 1 a row is the step's own values bit for bit); fields 13..18 are overwritten by
+ * every step, so they are those of the window's latest step. Only the last, open row can have
+ * STEPS < stride. CPU_SUM / MEM_SUM are the sums the `ut` reward is made of; the target means
+ * are recomputed from the state under every reward function (EnvHdr's own are left alone).
+ * With pm_rows, a second array f32[capacity][2 pms] per env keeps the PM part of the
+ * observation (cpu then memory, as vmp_get_obs emits them) of each window's latest step: the
+ * data of Base.test's utilisation timeline.
+ * Meta int64[VMP_SR_NMETA] per env: FIRST = the timestep when the env's series started, COUNT =
+ * steps observed since, LOST = steps whose row was >= capacity (counted, not stored). The
+ * row index is read from COUNT on the device, so a replayed graph advances through the rows.
+ *
+ * vmp_series_enable: capacity = rows per env, 0 frees the series; stride >= 1 steps per row;
+ * pm_rows 0 / 1. Otherwise the series is (re)allocated and started at row 0 from the current
+ * state (FIRST = the current timestep). An invalid argument or a byte size that does not fit
+ * returns VMP_EINVAL, a failed allocation VMP_EOOM; both leave the handle (and an earlier
+ * series) exactly as before. The series asks the step for its reward only (a scratch f64[n_env]
+ * where the caller passes none), never for actions or validity flags. Stream-ordered behind the
+ * queued launches; it allocates, so it must not be made during capture, and a graph captured
+ * before it does not observe and must be recaptured.
+ * With the series on, vmp_reset restarts the series of exactly the envs it resets, vmp_restore
+ * restarts every env's (the series is not part of a snapshot), vmp_destroy frees it. */
+int vmp_series_enable(vmp_handle *h, int64_t capacity, int32_t stride, int32_t pm_rows);
+/* Rows per env (0 = off), steps per row and whether PM rows are kept; each nullable. */
+int vmp_series_info(const vmp_handle *h, int64_t *capacity, int32_t *stride, int32_t *pm_rows);
+/* Copy the series so far (non-destructive, stream-ordered): rows device
+ * f64[n_env][capacity][VMP_SR_NF], pm device f32[n_env][capacity][2 pms] (only with pm_rows),
+ * meta device int64[n_env][VMP_SR_NMETA], each nullable. VMP_ESTATE while the series is off, or
+ * for a pm buffer on a series without PM rows. */
+int vmp_series_read(vmp_handle *h, double *rows, float *pm, int64_t *meta);
 
 /* Fault injection (tests only): the n-th device allocation made by the
  * library from now on fails as out of memory (n = 0: off). Drives the

@@ -16,6 +16,7 @@
 #include "vmp_layout.h"
 #include "vmp_record.h"
 #include "vmp_reqlog.h"
+#include "vmp_series.h"
 #include "vmp_trace.h"
 
 using namespace vmp;
@@ -53,6 +54,11 @@ struct vmp_handle {
   // recorder on as well the two share rec_act / rec_valid
   bool rq_on;
   ReqArgs rq;
+  // per-step time series (vmp_series.hip), allocated by vmp_series_enable; it steps on
+  // the reward alone: sr_reward where the caller passes no buffer
+  bool sr_on;
+  SerArgs sr;
+  double *sr_reward;
   // per-env workload (vmp_set_workload); all null / 0 for a handle never given one
   double *wl;           // host f64 [N][2]: arrival_rate, service_length of every env
   PoisConst *wl_rec;    // host mirror of pois_env
@@ -141,6 +147,38 @@ int reqlog_init(vmp_handle *h, const uint8_t *env_mask) {
   const int64_t blocks = (n + 255) / 256;
   hipLaunchKernelGGL(k_reqlog_init, dim3((unsigned)(blocks < (1 << 20) ? blocks : (1 << 20))), dim3(256),
                      0, h->stream, h->prm, h->rq, env_mask);
+  return launched();
+}
+
+// (re)start the time series of the envs flagged in env_mask (device, null = all)
+int series_init(vmp_handle *h, const uint8_t *env_mask) {
+  const int64_t per = h->sr.pm && 2 * (int64_t)h->P > VMP_SR_NF ? 2 * (int64_t)h->P : VMP_SR_NF;
+  const int64_t n = (int64_t)h->N * h->sr.cap * per;
+  const int64_t blocks = (n + 255) / 256;
+  hipLaunchKernelGGL(k_series_init, dim3((unsigned)(blocks < (1 << 20) ? blocks : (1 << 20))), dim3(256),
+                     0, h->stream, h->prm, h->sr, env_mask);
+  return launched();
+}
+
+// k_series where its static LDS holds the env, else k_series_lds on a private carve
+bool series_wave(const vmp_handle *h) { return h->V <= kMaxVPT * kWaveSize && h->P <= 1024; }
+// k_series_lds's dynamic LDS: carve_target_means' regions in q, then the used-PM bitmap
+size_t series_lds(const vmp_handle *h, EnvParams &q, int32_t *off_used) {
+  q = h->prm;
+  *off_used = (int32_t)align16((int64_t)carve_target_means(q));
+  return (size_t)*off_used + sizeof(uint64_t) * (size_t)((h->P + 63) / 64);
+}
+
+int launch_series(vmp_handle *h, const double *reward) {
+  SerArgs a = h->sr;
+  a.reward = reward;
+  if (series_wave(h)) {
+    hipLaunchKernelGGL(k_series, dim3((h->N + 3) / 4), dim3(256), 0, h->stream, h->prm, a);
+    return launched();
+  }
+  EnvParams q;
+  const size_t lds = series_lds(h, q, &a.off_used);
+  hipLaunchKernelGGL(k_series_lds, dim3(h->N), dim3(64), lds, h->stream, q, a);
   return launched();
 }
 
@@ -280,6 +318,7 @@ int vmp_destroy(vmp_handle *h) {
   std::free(h->tr_host);
   std::free(h->tr_map);
   std::free(h->tr_info);
+  vmp_series_enable(h, 0, 1, 0);
   vmp_reqlog_enable(h, 0);
   vmp_record_enable(h, 0);
   delete h;
@@ -540,13 +579,26 @@ int vmp_reset(vmp_handle *h, const int64_t *seeds, const uint8_t *env_mask, floa
   dim3 grid((h->N + kWavesPerBlock - 1) / kWavesPerBlock), block(64 * kWavesPerBlock);
   hipLaunchKernelGGL(k_reset, grid, block, 0, h->stream, h->prm, seeds, env_mask, obs);
   if (const int rc = launched()) return rc;
-  return h->rq_on ? reqlog_init(h, env_mask) : VMP_OK;  // the log of the envs just reset restarts
+  if (h->rq_on)  // the log of the envs just reset restarts
+    if (const int rc = reqlog_init(h, env_mask)) return rc;
+  return h->sr_on ? series_init(h, env_mask) : VMP_OK;  // ... and their time series
 }
 
 // One step; with recording on, the recorder (vmp_record.hip) after it, on the
 // handle's scratch action / validity / reward where the caller passes none;
 // with the request log on, its kernel (vmp_reqlog.hip) likewise
+static int step_observed(vmp_handle *h, StepOut o);
+// ... and behind them the time series (vmp_series.hip), which needs the step's reward
+// only: no actions or validity flags are asked for on its account, so a handle with
+// nothing else on keeps the step kernel's idle path
 static int step_recorded(vmp_handle *h, StepOut o) {
+  if (!h->sr_on) return step_observed(h, o);
+  if (!o.reward) o.reward = h->sr_reward;
+  if (const int rc = step_observed(h, o)) return rc;
+  return launch_series(h, o.reward);
+}
+
+static int step_observed(vmp_handle *h, StepOut o) {
   if (!h->rec_on && !h->rq_on) return launch_env(h, o);
   if (!o.actions && !o.act_out) o.act_out = h->rec_act;
   if (h->rec_on && !o.reward) o.reward = h->rec_reward;
@@ -637,7 +689,7 @@ int vmp_rollout_heuristic(vmp_handle *h, int32_t policy, int32_t k_steps, double
                           int64_t *done_count) {
   if (!h || k_steps < 1) return fail(VMP_EINVAL, "null handle or k_steps < 1");
   if (const int rc = check_policy(policy)) return rc;
-  if (h->rec_on || h->rq_on) {  // observed: one step per launch, the recorder / log after each
+  if (h->rec_on || h->rq_on || h->sr_on) {  // observed: one step per launch, the observers after each
     for (int32_t k = 0; k < k_steps; k++) {
       int rc = heuristic_step_impl(h, policy, nullptr, nullptr,
                                    rewards ? rewards + (int64_t)k * h->N : nullptr, nullptr,
@@ -770,6 +822,76 @@ int vmp_reqlog_read(vmp_handle *h, int32_t *rows, int64_t *meta) {
     if (const int rc = launched()) return rc;
   }
   if (meta) HIP_TRY(hipMemcpyAsync(meta, h->rq.meta, sz.meta, hipMemcpyDeviceToDevice, h->stream));
+  return VMP_OK;
+}
+
+// ---- per-step time series ----
+int vmp_series_enable(vmp_handle *h, int64_t capacity, int32_t stride, int32_t pm_rows) {
+  if (!h) return fail(VMP_EINVAL, "null handle");
+  if (capacity < 0) return fail(VMP_EINVAL, "vmp_series_enable: capacity must be >= 0");
+  if (capacity == 0) {
+    if (h->sr_on) (void)hipStreamSynchronize(h->stream);
+    for (void *q : {(void *)h->sr.rows, (void *)h->sr.pm, (void *)h->sr.meta, (void *)h->sr_reward})
+      dev_free(q);
+    std::memset(&h->sr, 0, sizeof(h->sr));
+    h->sr_reward = nullptr;
+    h->sr_on = false;
+    return VMP_OK;
+  }
+  SeriesSizes sz;
+  if (const char *why = series_sizes(h->N, h->P, capacity, stride, pm_rows, &sz))
+    return fail(VMP_EINVAL, why);
+  if (!series_wave(h)) {
+    EnvParams q;
+    int32_t off = 0;
+    if (series_lds(h, q, &off) > (size_t)64 * 1024)
+      return fail(VMP_EINVAL, "vmp_series_enable: config too large for the series kernel's LDS");
+  }
+  // a new set first: on any failure the handle, and a series it had, stay as they were
+  SerArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.cap = capacity;
+  a.stride = stride;
+  double *reward_new = nullptr;
+  const hipError_t e[4] = {
+      dev_malloc(&a.rows, sz.rows),
+      pm_rows ? dev_malloc(&a.pm, sz.pm) : hipSuccess,
+      dev_malloc(&a.meta, sz.meta),
+      h->sr_reward ? hipSuccess : dev_malloc(&reward_new, sz.reward)};
+  for (hipError_t x : e)
+    if (x != hipSuccess) {
+      for (void *b : {(void *)a.rows, (void *)a.pm, (void *)a.meta, (void *)reward_new}) dev_free(b);
+      return fail(x == hipErrorOutOfMemory ? VMP_EOOM : VMP_EDEVICE,
+                  std::string("vmp_series_enable: ") + hipGetErrorString(x));
+    }
+  if (h->sr_on) {  // queued launches write the series this one replaces
+    (void)hipStreamSynchronize(h->stream);
+    for (void *b : {(void *)h->sr.rows, (void *)h->sr.pm, (void *)h->sr.meta}) dev_free(b);
+  }
+  h->sr = a;
+  if (reward_new) h->sr_reward = reward_new;
+  h->sr_on = true;
+  return series_init(h, nullptr);
+}
+
+int vmp_series_info(const vmp_handle *h, int64_t *capacity, int32_t *stride, int32_t *pm_rows) {
+  if (!h) return fail(VMP_EINVAL, "null handle");
+  if (capacity) *capacity = h->sr_on ? h->sr.cap : 0;
+  if (stride) *stride = h->sr_on ? h->sr.stride : 0;
+  if (pm_rows) *pm_rows = h->sr_on && h->sr.pm ? 1 : 0;
+  return VMP_OK;
+}
+
+int vmp_series_read(vmp_handle *h, double *rows, float *pm, int64_t *meta) {
+  if (!h) return fail(VMP_EINVAL, "null handle");
+  if (!h->sr_on) return fail(VMP_ESTATE, "the time series is not enabled (vmp_series_enable)");
+  if (pm && !h->sr.pm) return fail(VMP_ESTATE, "the time series keeps no PM rows (pm_rows)");
+  SeriesSizes sz;
+  if (const char *why = series_sizes(h->N, h->P, h->sr.cap, h->sr.stride, h->sr.pm ? 1 : 0, &sz))
+    return fail(VMP_EINVAL, why);
+  if (rows) HIP_TRY(hipMemcpyAsync(rows, h->sr.rows, sz.rows, hipMemcpyDeviceToDevice, h->stream));
+  if (pm) HIP_TRY(hipMemcpyAsync(pm, h->sr.pm, sz.pm, hipMemcpyDeviceToDevice, h->stream));
+  if (meta) HIP_TRY(hipMemcpyAsync(meta, h->sr.meta, sz.meta, hipMemcpyDeviceToDevice, h->stream));
   return VMP_OK;
 }
 
@@ -947,7 +1069,9 @@ int vmp_restore(vmp_handle *h, const void *src) {
   HIP_TRY(hipMemcpyAsync(h->hdr, s + l.hdr, l.nh, hipMemcpyDeviceToDevice, h->stream));
   HIP_TRY(hipMemcpyAsync(h->pm, s + l.pm, l.np, hipMemcpyDeviceToDevice, h->stream));
   HIP_TRY(hipMemcpyAsync(h->vmw, s + l.vmw, l.nv, hipMemcpyDeviceToDevice, h->stream));
-  return h->rq_on ? reqlog_init(h, nullptr) : VMP_OK;  // the log is no part of a snapshot
+  if (h->rq_on)  // the log is no part of a snapshot
+    if (const int rc = reqlog_init(h, nullptr)) return rc;
+  return h->sr_on ? series_init(h, nullptr) : VMP_OK;  // nor is the time series
 }
 
 int64_t vmp_debug_live_allocs(void) { return g_live.load(); }

@@ -6,7 +6,7 @@ libvmp.so (HIP, gfx950); see include/vmp.h for the C ABI.
 """
 from .config import Config  # noqa: F401
 
-__all__ = ["Config", "VmEnv", "BatchedVmEnv", "register"]
+__all__ = ["Config", "VmEnv", "BatchedVmEnv", "Series", "register"]
 
 
 def __getattr__(name):  # lazy: importing torch-backed pieces needs a HIP device later
@@ -16,6 +16,9 @@ def __getattr__(name):  # lazy: importing torch-backed pieces needs a HIP device
     if name == "BatchedVmEnv":
         from .batched import BatchedVmEnv
         return BatchedVmEnv
+    if name == "Series":
+        from .series import Series
+        return Series
     raise AttributeError(name)
 
 

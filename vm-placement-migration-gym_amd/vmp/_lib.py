@@ -24,6 +24,7 @@ EXPORTS = (
     "vmp_actor_head_bf16_bwd_workspace", "vmp_actor_mlp_packed_floats", "vmp_actor_mlp_pack",
     "vmp_actor_mlp_f32", "vmp_actor_mlp_head_f32", "vmp_step_mask", "vmp_record_enable",
     "vmp_record_read", "vmp_reqlog_enable", "vmp_reqlog_info", "vmp_reqlog_read",
+    "vmp_series_enable", "vmp_series_info", "vmp_series_read",
     "vmp_snapshot_bytes", "vmp_snapshot", "vmp_restore",
     "vmp_debug_fail_alloc", "vmp_debug_live_allocs", "vmp_debug_stamps", "vmp_debug_occupancy",
     "vmp_debug_quiet_violations",
@@ -127,6 +128,9 @@ def lib():
         "vmp_reqlog_enable": (ctypes.c_int, [P, i64]),
         "vmp_reqlog_info": (ctypes.c_int, [P, P]),
         "vmp_reqlog_read": (ctypes.c_int, [P, P, P]),
+        "vmp_series_enable": (ctypes.c_int, [P, i64, i32, i32]),
+        "vmp_series_info": (ctypes.c_int, [P, P, P, P]),
+        "vmp_series_read": (ctypes.c_int, [P, P, P, P]),
         "vmp_snapshot_bytes": (ctypes.c_int, [P, P]),
         "vmp_snapshot": (ctypes.c_int, [P, P]),
         "vmp_restore": (ctypes.c_int, [P, P]),

@@ -378,6 +378,47 @@ class BatchedVmEnv:
         check(lib().vmp_reqlog_read(h, ptr(rows), ptr(meta)))
         return RequestLog(rows.cpu().numpy(), meta.cpu().numpy())
 
+    # ------------------------------------------------- per-step time series
+    def series(self, on=True, capacity=None, stride=1, pm_rows=False):
+        """Start (on=True) or free the per-step time series of every env on the
+        device (vmp_series_enable): one row per window of `stride` steps with
+        the reward, waiting ratio, PM utilisation, target means, used PMs and
+        counters (see vmp.series), filled after every step; pm_rows also keeps
+        the PMs' cpu and memory of each window's last step. capacity: rows per
+        env, by default what the steps left to eval_steps (training_steps
+        outside eval mode) need. The series starts at row 0 from the current
+        state; reset() restarts the series of the envs it resets. Not during
+        graph capture; a graph captured before the call does not observe."""
+        h = self._bind()
+        if not on:
+            check(lib().vmp_series_enable(h, 0, 1, 0))
+            return
+        if int(stride) < 1:
+            raise ValueError("stride must be >= 1")
+        if capacity is None:
+            limit = self.config.eval_steps if self.eval_mode else self.config.training_steps
+            left = int(limit) - (int(self.counters()[:, 5].min()) - 1)
+            capacity = max(1, -(-left // int(stride)))
+        if int(capacity) < 1:
+            raise ValueError("capacity must be >= 1")
+        with torch.cuda.device(self.device):
+            check(lib().vmp_series_enable(h, int(capacity), int(stride), int(bool(pm_rows))))
+
+    def series_read(self):
+        """The series so far as a `vmp.series.Series` (non-destructive)."""
+        from .series import NF, NMETA, Series
+        h = self._bind()
+        cap, stride, pmr = ctypes.c_int64(), ctypes.c_int32(), ctypes.c_int32()
+        check(lib().vmp_series_info(h, ctypes.byref(cap), ctypes.byref(stride), ctypes.byref(pmr)))
+        if cap.value == 0:
+            raise VmpError("the time series is not enabled (series())")
+        rows = self._empty((self.n_envs, cap.value, NF), torch.float64)
+        meta = self._empty((self.n_envs, NMETA), torch.int64)
+        pm = self._empty((self.n_envs, cap.value, 2 * self.P), torch.float32) if pmr.value else None
+        check(lib().vmp_series_read(h, ptr(rows), ptr(pm), ptr(meta)))
+        return Series(rows.cpu().numpy(), meta.cpu().numpy(), stride.value,
+                      None if pm is None else pm.cpu().numpy())
+
     def rank(self):
         h = self._bind()
         r = self._empty((self.n_envs,), torch.int64)

@@ -15,6 +15,7 @@ comes back to the host. This replaces the reference's process fan-out
     python -m vmp.exp migration_ratio --agents bestfit,ppo --weights 'w/ppo-{reward}.pt'
     python -m vmp.exp paired --trace a.npz,b.npz           # every agent on the same requests
     python -m vmp.exp paired --trace a.npz --requests r.csv   # ... and what became of each request
+    python -m vmp.exp suspension --series s.csv --series-stride 100   # any experiment: curves over time
 
 Rows are printed in exp_suspension.py's CSV layout (exp_suspension.py:51-58):
 Agent, Load, Service Length, Total Served, Valid Suspend Actions, Valid
@@ -112,8 +113,48 @@ def merge_groups(cells, cfgs, merge=True):
     return groups
 
 
+# ------------------------------------------------------------ time series
+def _series_fields():
+    from .series import COUNTERS, SUMMED
+    return SUMMED + tuple(c for c in COUNTERS if c != "timestep")
+
+
+def series_header():
+    return "Cell, Agent, Envs, Window, Timestep" + "".join(
+        ", %s Mean, %s Std" % (f, f) for f in _series_fields())
+
+
+def series_rows(index, name, ser):
+    """One CSV row per window of a cell's `vmp.series.Series` (its envs are the
+    cell's seeds): the cell's index and name, its env count, the window, the
+    timestep counter after the window's last step, then the mean and the std
+    over the envs of every field's window mean (Series.band; floats in repr)."""
+    bands = [ser.band(f) for f in _series_fields()]
+    ts = ser.timestep[0] if ser.n_envs else []
+    rows = []
+    for r in range(len(bands[0][0])):
+        rows.append("%d,%s,%d,%d,%d" % (index, name, ser.n_envs, r, int(ts[r])) + "".join(
+            ",%r,%r" % (float(m[r]), float(sd[r])) for m, sd in bands))
+    return rows
+
+
+def _series_request(series):
+    """(stride, path) of a `series=` argument, None for none."""
+    if series is None:
+        return None
+    stride, path = series
+    if int(stride) < 1:
+        raise ValueError("series stride must be >= 1")
+    return int(stride), path
+
+
+def _write_series(path, rows):
+    with open(path, "w") as f:
+        f.write("\n".join([series_header()] + rows) + "\n")
+
+
 def run_cells(cells, make_config=None, eval_steps=None, chunk=2000, device="cuda:0",
-              graph_steps=100, merge=False):
+              graph_steps=100, merge=False, series=None):
     """Evaluate every cell (Base.test per seed, base.py:63-118) for its eval_steps
     and return one list of Record summaries per cell (one dict per seed). All
     seeds of a cell are the envs of one handle, so the recorder's cross-env sums
@@ -122,7 +163,13 @@ def run_cells(cells, make_config=None, eval_steps=None, chunk=2000, device="cuda
     merge=True: the cells of one merge_groups group are the envs of ONE handle
     (their seeds concatenated, each env at its cell's arrival rate and service
     length), with one recorder and one captured rollout; the return value keeps
-    its shape, except that `_xmem` (a sum over a handle's envs) is NaN."""
+    its shape, except that `_xmem` (a sum over a handle's envs) is NaN.
+    series=(stride, path): also keep the per-step time series of every env on
+    the device (BatchedVmEnv.series, `stride` steps a window) and write one
+    row per cell and window to the CSV `path` (series_header / series_rows);
+    merged cells still report their own envs."""
+    series = _series_request(series)
+    series_out = {}
     cfgs = []
     for cell in cells:
         cfg = dict(cell.cfg) if cell.cfg is not None else make_config(cell.load, cell.service_length)
@@ -144,6 +191,8 @@ def run_cells(cells, make_config=None, eval_steps=None, chunk=2000, device="cuda
             env.eval(True)
             env.reset(torch.tensor(seeds, dtype=torch.int64))
             env.record(True)  # before the graph capture, so replays are recorded too
+            if series:
+                env.series(True, capacity=-(-int(cfg["eval_steps"]) // series[0]), stride=series[0])
             agent = None
             if cell.agent == "ppo":
                 from .ppo import ActStepGraph, PPOAgent, PPOConfig
@@ -176,11 +225,17 @@ def run_cells(cells, make_config=None, eval_steps=None, chunk=2000, device="cuda
     for g, env, s in zip(groups, envs, streams):
         with torch.cuda.stream(s):
             summ = env.record_summary()
+            ser = env.series_read() if series else None
         env.close()
         at = 0
         for i in g:
             out[i] = summ[at:at + len(cells[i].seeds)]
+            if series:
+                series_out[i] = series_rows(i, cells[i].name or cells[i].agent,
+                                            ser.env(slice(at, at + len(cells[i].seeds))))
             at += len(cells[i].seeds)
+    if series:
+        _write_series(series[1], [r for i in sorted(series_out) for r in series_out[i]])
     if merge:
         for summ in out:
             for d in summ:
@@ -199,7 +254,7 @@ def suspension_row(cell, summaries):
 
 
 def suspension_sweep(agents=("firstfit", "bestfit"), loads=None, lengths=None, seeds=(0,),
-                     weights=None, eval_steps=None, merge=False):
+                     weights=None, eval_steps=None, merge=False, series=None):
     """The exp_suspension.py grid (load 1.0 x service lengths 100..3900 step 200,
     then service length 1000 x loads 0.2..1.0) for the given agents. merge=True
     runs each heuristic agent's whole grid as the envs of one handle (run_cells)."""
@@ -211,7 +266,7 @@ def suspension_sweep(agents=("firstfit", "bestfit"), loads=None, lengths=None, s
              for sr in lengths for a in agents]
     cells += [Cell(a, float(ld), 1000, tuple(seeds), weights if a == "ppo" else None)
               for ld in loads for a in agents]
-    res = run_cells(cells, suspension_config, eval_steps=eval_steps, merge=merge)
+    res = run_cells(cells, suspension_config, eval_steps=eval_steps, merge=merge, series=series)
     return [suspension_row(c, r) for c, r in zip(cells, res)]
 
 
@@ -231,18 +286,22 @@ def paired_row(agent, index, trace, summary):
 
 
 def paired_sweep(traces, agents=("firstfit", "bestfit"), config=None, eval_steps=None,
-                 weights=None, device="cuda:0"):
+                 weights=None, device="cuda:0", series=None):
     """Every agent on the SAME requests: one handle per agent whose env i replays
     traces[i] (BatchedVmEnv.set_trace), the device recorder on, eval_steps steps
     (default: the longest trace). A traced env's requests do not depend on what
     the policy did with the earlier ones, so the rows of one trace compare the
-    agents on one workload. One CSV row per (agent, trace), see PAIRED_HEADER."""
-    return _paired_run(traces, agents, config, eval_steps, weights, device, False)[0]
+    agents on one workload. One CSV row per (agent, trace), see PAIRED_HEADER.
+    series=(stride, path): also write the time series CSV, one row per agent
+    and window over the agent's envs (run_cells)."""
+    return _paired_run(traces, agents, config, eval_steps, weights, device, False, series)[0]
 
 
-def _paired_run(traces, agents, config, eval_steps, weights, device, log):
+def _paired_run(traces, agents, config, eval_steps, weights, device, log, series=None):
     """paired_sweep's runs; log=True: with the per-request outcome log on.
     Returns (rows, {agent: RequestLog})."""
+    series = _series_request(series)
+    series_out = []
     traces = list(traces)
     cfg = dict(ENV100, reward_function="wr") if config is None else dict(config)
     steps = int(eval_steps) if eval_steps is not None else max(t.steps for t in traces)
@@ -258,6 +317,8 @@ def _paired_run(traces, agents, config, eval_steps, weights, device, log):
         env.record(True)
         if log:  # before the capture below: a graph captured earlier would not log
             env.request_log(True)
+        if series:
+            env.series(True, capacity=-(-steps // series[0]), stride=series[0])
         if name == "ppo":
             from .ppo import ActStepGraph, PPOAgent, PPOConfig
             ag = PPOAgent(env, PPOConfig(**PPO100))
@@ -271,8 +332,12 @@ def _paired_run(traces, agents, config, eval_steps, weights, device, log):
         summ = env.record_summary()
         if log:
             logs[name] = env.request_log_read()
+        if series:
+            series_out += series_rows(list(agents).index(name), name, env.series_read())
         env.close()
         rows += [paired_row(name, i, t, s) for i, (t, s) in enumerate(zip(traces, summ))]
+    if series:
+        _write_series(series[1], series_out)
     return rows, logs
 
 
@@ -394,11 +459,11 @@ def performance_row(cell, summaries):
         f("_mean_pending"), f("_waiting"), f("_mean_slowdown"))
 
 
-def performance_sweep(cells, eval_steps=None, merge=False):
+def performance_sweep(cells, eval_steps=None, merge=False, series=None):
     if merge:  # Memory Variance needs the recorder's sums over exactly a cell's seeds
         raise ValueError("performance_sweep cannot merge cells: its Memory Variance column "
                          "is a cross-env sum over one handle's envs (_xmem)")
-    res = run_cells(cells, eval_steps=eval_steps)
+    res = run_cells(cells, eval_steps=eval_steps, series=series)
     return [performance_row(c, r) for c, r in zip(cells, res)]
 
 
@@ -433,8 +498,8 @@ def vm_size_row(cell, summaries):
         f("_mem_var"), f("_waiting"))
 
 
-def vm_size_sweep(cells, eval_steps=None):
-    res = run_cells(cells, eval_steps=eval_steps)
+def vm_size_sweep(cells, eval_steps=None, series=None):
+    res = run_cells(cells, eval_steps=eval_steps, series=series)
     return [vm_size_row(c, r) for c, r in zip(cells, res)]
 
 
@@ -470,8 +535,8 @@ def reward_row(cell, summaries):
         f("_mem_mean"), f("_mem_var"), f("_mean_pending"), f("_waiting"), f("_mean_slowdown"))
 
 
-def reward_sweep(cells, eval_steps=None):
-    res = run_cells(cells, eval_steps=eval_steps)
+def reward_sweep(cells, eval_steps=None, series=None):
+    res = run_cells(cells, eval_steps=eval_steps, series=series)
     return [reward_row(c, r) for c, r in zip(cells, res)]
 
 
@@ -489,12 +554,12 @@ def migration_row(cell, summaries):
                                      s["_mean_slowdown"])
 
 
-def migration_sweep(cells, eval_steps=None):
-    res = run_cells(cells, eval_steps=eval_steps)
+def migration_sweep(cells, eval_steps=None, series=None):
+    res = run_cells(cells, eval_steps=eval_steps, series=series)
     return [migration_row(c, r) for c, r in zip(cells, res)]
 
 
-def main(argv=None):
+def arg_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("experiment", choices=["suspension", "performance", "performance_small",
                                            "vm_size", "reward", "migration_ratio", "paired"])
@@ -514,8 +579,20 @@ def main(argv=None):
     ap.add_argument("--requests", default=None,
                     help="paired: also write one row per (trace, request) to this CSV and print "
                          "the per-request paired differences")
+    ap.add_argument("--series", default=None,
+                    help="any experiment: also write the per-step time series to this CSV, one "
+                         "row per cell (per agent for paired) and window")
+    ap.add_argument("--series-stride", type=int, default=1, help="steps per window of --series")
     ap.add_argument("--out", default=None)
+    return ap
+
+
+def main(argv=None):
+    ap = arg_parser()
     a = ap.parse_args(argv)
+    if a.series_stride < 1:
+        ap.error("--series-stride must be >= 1")
+    series = None if a.series is None else (a.series_stride, a.series)
     agents = a.agents.split(",")
     seeds = None if a.seeds is None else [int(x) for x in a.seeds.split(",")]
     loads = None if a.loads is None else [float(x) for x in a.loads.split(",")]
@@ -533,7 +610,7 @@ def main(argv=None):
         header = PAIRED_HEADER
         traces = [Trace.load(p) for p in a.trace.split(",")]
         rows, logs = _paired_run(traces, agents, cfg, a.eval_steps, a.weights, "cuda:0",
-                                 a.requests is not None)
+                                 a.requests is not None, series)
         if a.requests is not None:
             with open(a.requests, "w") as f:
                 f.write("\n".join([paired_requests_header(agents)]
@@ -544,7 +621,8 @@ def main(argv=None):
         rows = suspension_sweep(
             agents=agents, loads=loads,
             lengths=None if a.lengths is None else [int(x) for x in a.lengths.split(",")],
-            seeds=seeds or [0], weights=a.weights, eval_steps=a.eval_steps, merge=a.merge)
+            seeds=seeds or [0], weights=a.weights, eval_steps=a.eval_steps, merge=a.merge,
+            series=series)
     elif a.experiment in ("performance", "performance_small"):
         header = PERFORMANCE_HEADER
         small = a.experiment == "performance_small"
@@ -552,14 +630,14 @@ def main(argv=None):
         cells = [performance_cell(ag, "ppo-" + reward if ag == "ppo" else ag, ld, reward,
                                   a.weights if ag == "ppo" else None, small, seeds)
                  for ld in (loads or [1.0]) for ag in agents]
-        rows = performance_sweep(cells, eval_steps=a.eval_steps, merge=a.merge)
+        rows = performance_sweep(cells, eval_steps=a.eval_steps, merge=a.merge, series=series)
     elif a.experiment == "reward":
         header = REWARD_HEADER
         rewards = a.reward.split(",") if a.reward else ["wr", "ut", "kl"]
         cells = [reward_cell(ag, rw, a.weights.replace("{reward}", rw) if ag == "ppo" else None,
                              seeds=tuple(seeds) if seeds else tuple(range(5)))
                  for ag in agents for rw in rewards]
-        rows = reward_sweep(cells, eval_steps=a.eval_steps)
+        rows = reward_sweep(cells, eval_steps=a.eval_steps, series=series)
     elif a.experiment == "migration_ratio":
         header = MIGRATION_HEADER
         ratios = [round(0.001 * i, 3) for i in range(10)]
@@ -567,13 +645,13 @@ def main(argv=None):
                                 if ag == "ppo" else None)
                  for r in ratios for ag in agents
                  for rw in (["ut"] if ag != "ppo" else ["wr", "ut", "kl"])]
-        rows = migration_sweep(cells, eval_steps=a.eval_steps)
+        rows = migration_sweep(cells, eval_steps=a.eval_steps, series=series)
     else:
         header = VM_SIZE_HEADER
         cells = [vm_size_cell(ag, seq, a.weights if ag == "ppo" else None,
                               tuple(seeds) if seeds else tuple(range(5)))
                  for seq in ("lowuniform", "highuniform") for ag in agents]
-        rows = vm_size_sweep(cells, eval_steps=a.eval_steps)
+        rows = vm_size_sweep(cells, eval_steps=a.eval_steps, series=series)
     text = header + "\n" + "\n".join(rows) + "\n"
     if a.out:
         with open(a.out, "w") as f:
