@@ -481,7 +481,13 @@ int64_t vmp_actor_head_bf16_bwd_workspace(int32_t B, int32_t V, int32_t A);
  * on = 1 allocates the recorder and starts it from the current state (call it
  * right after reset, as Base.test records from reset); every later vmp_step /
  * vmp_heuristic_step / vmp_rollout_heuristic step is recorded for every env.
- * on = 0 frees it. */
+ * While it is on, vmp_reset restarts the recorder of exactly the envs it
+ * resets (previous placement from the reset state, no open lives, zero hist
+ * and sums; the other envs' records go on), and vmp_restore restarts every
+ * env's recorder from the restored state (a recorder is no part of a
+ * snapshot): what the request log and the time series do. A VM present when a
+ * recorder (re)starts has no arrival on record: its life starts with length 0
+ * and grows from the next recorded step. on = 0 frees it. */
 int vmp_record_enable(vmp_handle *h, int32_t on);
 /* Read the metrics so far (non-destructive): hist u32[n_env][2][VMP_REC_BINS]
  * = counts of the pending and slowdown rates rounded to 3 decimals (x1000),

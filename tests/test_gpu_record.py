@@ -3,7 +3,13 @@ every published firstfit/bestfit row of data/exp_suspension/data.csv (100k-step
 evals of config/100.yml: served, valid suspends, valid actions, mean life,
 mean pending, mean/max slowdown) and the literal host restatement of
 record.py (tests/record_literal.py, fed by Base.record_testing_step from
-eval-mode info) on a trajectory with random suspensions and placements."""
+eval-mode info) on a trajectory with random suspensions and placements.
+
+That literal is fed by device read-backs: VmEnv.step's info takes placements,
+PM loads, rank, waiting ratio and target means from the device and derives
+vm_arrival_steps by the very rule k_record uses, so the arrival derivation is
+compared with itself there. tests/test_gpu_record_truth.py compares the
+recorder with a ground truth that reads nothing back (tests/record_truth.py)."""
 import csv
 import os
 

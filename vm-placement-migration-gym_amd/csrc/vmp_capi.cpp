@@ -140,6 +140,16 @@ void scratch_free(vmp_handle *h) {
   h->rec_valid = nullptr;
 }
 
+// (re)start the recorder of the envs flagged in env_mask (device, null = all)
+int record_init(vmp_handle *h, const uint8_t *env_mask) {
+  size_t n = (size_t)h->N * h->V;
+  if ((size_t)h->N * 2 * VMP_REC_BINS > n) n = (size_t)h->N * 2 * VMP_REC_BINS;
+  if ((size_t)h->N * VMP_NREC > n) n = (size_t)h->N * VMP_NREC;
+  hipLaunchKernelGGL(k_record_init, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream,
+                     h->prm, h->rec, env_mask);
+  return launched();
+}
+
 // (re)start the request log of the envs flagged in env_mask (device, null = all)
 int reqlog_init(vmp_handle *h, const uint8_t *env_mask) {
   const int64_t rows = h->rq.cap * VMP_RQ_NF;
@@ -579,7 +589,9 @@ int vmp_reset(vmp_handle *h, const int64_t *seeds, const uint8_t *env_mask, floa
   dim3 grid((h->N + kWavesPerBlock - 1) / kWavesPerBlock), block(64 * kWavesPerBlock);
   hipLaunchKernelGGL(k_reset, grid, block, 0, h->stream, h->prm, seeds, env_mask, obs);
   if (const int rc = launched()) return rc;
-  if (h->rq_on)  // the log of the envs just reset restarts
+  if (h->rec_on)  // the recorder of the envs just reset restarts
+    if (const int rc = record_init(h, env_mask)) return rc;
+  if (h->rq_on)  // ... and so does their log
     if (const int rc = reqlog_init(h, env_mask)) return rc;
   return h->sr_on ? series_init(h, env_mask) : VMP_OK;  // ... and their time series
 }
@@ -745,12 +757,7 @@ int vmp_record_enable(vmp_handle *h, int32_t on) {
                     std::string("vmp_record_enable: ") + hipGetErrorString(x));
       }
   }
-  size_t n = nv;
-  if ((size_t)h->N * 2 * VMP_REC_BINS > n) n = (size_t)h->N * 2 * VMP_REC_BINS;
-  if ((size_t)h->N * VMP_NREC > n) n = (size_t)h->N * VMP_NREC;
-  hipLaunchKernelGGL(k_record_init, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream,
-                     h->prm, h->rec);
-  HIP_TRY(hipGetLastError());
+  if (const int rc = record_init(h, nullptr)) return rc;
   h->rec_on = true;
   return VMP_OK;
 }
@@ -1069,7 +1076,9 @@ int vmp_restore(vmp_handle *h, const void *src) {
   HIP_TRY(hipMemcpyAsync(h->hdr, s + l.hdr, l.nh, hipMemcpyDeviceToDevice, h->stream));
   HIP_TRY(hipMemcpyAsync(h->pm, s + l.pm, l.np, hipMemcpyDeviceToDevice, h->stream));
   HIP_TRY(hipMemcpyAsync(h->vmw, s + l.vmw, l.nv, hipMemcpyDeviceToDevice, h->stream));
-  if (h->rq_on)  // the log is no part of a snapshot
+  if (h->rec_on)  // the recorder is no part of a snapshot: it restarts from the restored state
+    if (const int rc = record_init(h, nullptr)) return rc;
+  if (h->rq_on)  // nor is the log
     if (const int rc = reqlog_init(h, nullptr)) return rc;
   return h->sr_on ? series_init(h, nullptr) : VMP_OK;  // nor is the time series
 }

@@ -19,7 +19,8 @@ struct RecArgs {
   const double *reward;    // [N]
 };
 __global__ void k_record(EnvParams p, RecArgs r);
-__global__ void k_record_init(EnvParams p, RecArgs r);
+// env_mask (device u8 [N], nullable = all): the envs to (re)start
+__global__ void k_record_init(EnvParams p, RecArgs r, const uint8_t *env_mask);
 __global__ void k_record_close(EnvParams p, RecArgs r, uint32_t *hist, double *sums);
 
 // per-request outcome log (vmp_reqlog.hip), a second observer behind the step

@@ -179,18 +179,19 @@ __global__ __launch_bounds__(256) void k_record(EnvParams p, RecArgs r) {
   }
 }
 
-// Start recording: previous placement = current, no open lives, zero sums.
-__global__ void k_record_init(EnvParams p, RecArgs r) {
+// Start recording, for every env (of those flagged in env_mask): previous
+// placement = current, no open lives, zero sums.
+__global__ void k_record_init(EnvParams p, RecArgs r, const uint8_t *env_mask) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int64_t nv = (int64_t)p.N * p.V;
-  if (i < nv) {
+  if (i < nv && (!env_mask || env_mask[i / p.V])) {
     r.prev[i] = (uint16_t)(p.vmw[(i / p.V) * vm_pitch(p.V) + vm_slot_idx((int)(i % p.V))] & 0xFFFFu);
     r.life_n[i] = 0;
     r.alloc[i] = -1;
     r.waits[i] = 0;
   }
-  if (i < (int64_t)p.N * 2 * kRecBins) r.hist[i] = 0;
-  if (i < (int64_t)p.N * VMP_NREC) r.sums[i] = 0.0;
+  if (i < (int64_t)p.N * 2 * kRecBins && (!env_mask || env_mask[i / (2 * kRecBins)])) r.hist[i] = 0;
+  if (i < (int64_t)p.N * VMP_NREC && (!env_mask || env_mask[i / VMP_NREC])) r.sums[i] = 0.0;
 }
 
 // Read-out (after vmp_record_read copied hist/sums into the caller's buffers):

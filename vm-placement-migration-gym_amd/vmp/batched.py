@@ -321,11 +321,14 @@ class BatchedVmEnv:
     # ------------------------------------------------ eval-mode Record metrics
     def record(self, on=True):
         """Start (on=True, right after reset, as Base.test does) or stop recording
-        the Record metrics of every env on the device (vmp_record_enable)."""
+        the Record metrics of every env on the device (vmp_record_enable).
+        reset() restarts the recorder of the envs it resets, restore() that of
+        every env."""
         check(lib().vmp_record_enable(self._bind(), int(bool(on))))
 
     def record_read(self):
-        """(hist u32 [N, 2, 1001] pending/slowdown rate counts, sums f64 [N, 16])."""
+        """(hist u32 [N, 2, 1001] pending/slowdown rate counts, sums f64 [N, 19]:
+        include/vmp.h VMP_REC_*). Non-destructive."""
         h = self._bind()
         hist = self._empty((self.n_envs, 2, REC_BINS), torch.int32)
         sums = self._empty((self.n_envs, N_REC), torch.float64)
