@@ -604,6 +604,20 @@ int vmp_debug_quiet_violations(int64_t *count);
  * the LDS bytes it is launched with (dynamic + static). */
 int vmp_debug_occupancy(vmp_handle *h, int32_t *blocks_per_cu, int32_t *lds_bytes);
 
+/* Diagnostics: the order in which the workgroups of the per-step launches of
+ * the wave kernels (V <= 1024) take the envs. 0: index order; 1: every other
+ * launch walks the envs downwards; 2: as 1, and the heuristic per-step launch
+ * hands the envs that were not idle after the previous launch to workgroups
+ * dispatched early. Results do not depend on the mode. A new handle starts in
+ * mode 2; for measurements VMP_LAUNCH_ORDER=<mode>[:<tail divisor>] in the
+ * environment of vmp_create overrides that. */
+int vmp_debug_launch_order(vmp_handle *h, int32_t mode);
+/* What the next heuristic per-step launch would do: env_of_block device
+ * int32[n_env], the env each workgroup takes; flags_read device
+ * uint8[64 * ceil(n_env / 64)], the flag bytes [chunk][rank] it decides on
+ * (non-zero: not idle). Stream-ordered; counts as no launch. */
+int vmp_debug_launch_map(vmp_handle *h, int32_t *env_of_block, uint8_t *flags_read);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,6 +13,7 @@
 #include "vmp_carve.h"
 #include "vmp_host.h"
 #include "vmp_kernels.h"
+#include "vmp_launch_order.h"
 #include "vmp_layout.h"
 #include "vmp_record.h"
 #include "vmp_reqlog.h"
@@ -75,6 +76,11 @@ struct vmp_handle {
   int32_t *tr_map;      // host [N]
   int64_t *tr_info;     // host [tr_n][2]: steps, requests
   uint64_t tr_hash;     // content hash of (traces, map), carried by snapshots
+  // launch order of the per-step wave launches (vmp_launch_order.h): their count
+  // (its low bit is the next launch's parity), the mode and the tail divisor; the
+  // two flag buffers lie behind hdr. None of it is part of a snapshot.
+  uint32_t lo_count;
+  int32_t lo_mode, lo_div;
 };
 
 namespace {
@@ -96,6 +102,11 @@ EnvKernel env_kernel(bool ext, bool one, bool wl, bool tr) {
   return wl ? k_env<VPT, false, true> : k_env<VPT, false, false>;
 }
 
+// EnvParams::pad0 of the next per-step wave launch
+uint32_t launch_order_word(const vmp_handle *h) {
+  return lo_word(h->lo_mode, (int)(h->lo_count & 1u), h->N, lo_tail(h->N, h->lo_div));
+}
+
 int launch_env(vmp_handle *h, const StepOut &o) {
   dim3 grid((h->N + kEnvWavesPerBlock - 1) / kEnvWavesPerBlock), block(64 * kEnvWavesPerBlock);
   EnvParams p = h->prm;
@@ -113,6 +124,10 @@ int launch_env(vmp_handle *h, const StepOut &o) {
   }
   // external actions: vmp_step, one step
   if (o.actions && o.k_steps != 1) return fail(VMP_EINVAL, "external actions take one step per launch");
+  if (o.k_steps == 1) {  // per-step launches alternate their direction (vmp_launch_order.h)
+    p.pad0 = (int32_t)launch_order_word(h);
+    h->lo_count++;
+  }
   const int need = (h->V + 63) / 64;  // the fewest of 1 / 2 / 4 / 8 / 16 rows that hold V
   const auto pick = need <= 1 ? env_kernel<1> : need <= 2 ? env_kernel<2> : need <= 4 ? env_kernel<4>
                     : need <= 8 ? env_kernel<8> : env_kernel<16>;
@@ -246,10 +261,18 @@ int vmp_create(const vmp_config *cfg, int32_t n_env, const int64_t *seeds, int32
 static int create_rest(vmp_handle *h, const vmp_config *cfg, int32_t n_env, const int64_t *seeds) {
   hipError_t e1 = dev_malloc(&h->vmw, sizeof(uint32_t) * (size_t)n_env * vm_pitch(h->V));
   hipError_t e2 = dev_malloc(&h->pm, sizeof(double) * (size_t)n_env * 2 * h->P);
-  hipError_t e3 = dev_malloc(&h->hdr, sizeof(EnvHdr) * (size_t)n_env);
+  // the headers, then the two flag buffers of the launch order (zero: every env idle)
+  const size_t hdr_bytes = sizeof(EnvHdr) * (size_t)n_env + 2 * (size_t)lo_flag_bytes(n_env);
+  hipError_t e3 = dev_malloc(&h->hdr, hdr_bytes);
   if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess)
     return fail(VMP_EOOM, "device allocation failed");
-  HIP_TRY(hipMemset(h->hdr, 0, sizeof(EnvHdr) * (size_t)n_env));
+  HIP_TRY(hipMemset(h->hdr, 0, hdr_bytes));
+  h->lo_mode = kLoDefaultMode;
+  h->lo_div = kLoDefaultDiv;
+  if (const char *m = getenv("VMP_LAUNCH_ORDER")) {  // measurement: "<mode>" or "<mode>:<divisor>"
+    if (m[0] >= '0' && m[0] <= '2') h->lo_mode = m[0] - '0';
+    if (m[0] && m[1] == ':' && atoi(m + 2) >= 4) h->lo_div = atoi(m + 2);
+  }
   EnvParams &p = h->prm;
   p.N = h->N;
   p.P = h->P;
@@ -1084,6 +1107,26 @@ int vmp_restore(vmp_handle *h, const void *src) {
 }
 
 int64_t vmp_debug_live_allocs(void) { return g_live.load(); }
+
+int vmp_debug_launch_order(vmp_handle *h, int32_t mode) {
+  if (!h) return fail(VMP_EINVAL, "null handle");
+  if (mode < kLoIndex || mode > kLoIdleLast) return fail(VMP_EINVAL, "launch order mode must be 0, 1 or 2");
+  h->lo_mode = mode;
+  return VMP_OK;
+}
+
+int vmp_debug_launch_map(vmp_handle *h, int32_t *env_of_block, uint8_t *flags_read) {
+  if (!h || !env_of_block || !flags_read) return fail(VMP_EINVAL, "null argument");
+  if (h->big) return fail(VMP_EINVAL, "the block kernel (V > 1024) keeps index order");
+  EnvParams p = h->prm;
+  p.pad0 = (int32_t)launch_order_word(h);
+  hipLaunchKernelGGL(k_launch_map, dim3(h->N), dim3(64), 0, h->stream, p, env_of_block);
+  if (const int rc = launched()) return rc;
+  const size_t nb = (size_t)lo_flag_bytes(h->N);
+  const uint8_t *flags = reinterpret_cast<const uint8_t *>(h->hdr + h->N) + nb * (h->lo_count & 1u);
+  HIP_TRY(hipMemcpyAsync(flags_read, flags, nb, hipMemcpyDeviceToDevice, h->stream));
+  return VMP_OK;
+}
 
 int vmp_debug_quiet_violations(int64_t *count) {
   if (!count) return fail(VMP_EINVAL, "null argument");

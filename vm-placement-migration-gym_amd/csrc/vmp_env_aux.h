@@ -231,6 +231,15 @@ __global__ __launch_bounds__(64) void k_target_means_lds(EnvParams p) {
   }
 }
 
+// vmp_debug_launch_map: the env each workgroup of a heuristic per-step launch
+// with p.pad0 takes, by the function the launch itself evaluates (one wave per
+// workgroup, as there); env state is neither read nor written.
+__global__ __launch_bounds__(64) void k_launch_map(EnvParams p, int32_t *env_of_block) {
+  int fidx;
+  const int e = uni(lo_swap_env(p, lo_position((uint32_t)p.pad0, p.N, (int)blockIdx.x), fidx));
+  if (lane_id() == 0) env_of_block[blockIdx.x] = e;
+}
+
 }  // namespace vmp
 
 #endif  // VMP_ENV_AUX_H

@@ -10,6 +10,7 @@
 #include "vmp_dev.h"
 #include "vmp_env_common.h"
 #include "vmp_kernels.h"
+#include "vmp_launch_order.h"
 #include "vmp_layout.h"
 #include "vmp_stamps.h"
 
@@ -583,6 +584,46 @@ __device__ __forceinline__ void write_mask(const EnvParams &p, const Lds &L, con
   }
 }
 
+// ---- launch order of the per-step launches (vmp_launch_order.h) -----------
+// The two flag buffers lie behind the handle's headers, [parity][chunk][rank].
+__device__ __forceinline__ uint8_t *lo_flags(const EnvParams &p, int parity) {
+  return reinterpret_cast<uint8_t *>(p.hdr + p.N) + (int64_t)parity * lo_flag_bytes(p.N);
+}
+// The env that dispatch position q of the heuristic per-step kernel runs
+// (wave-uniform, scalar but for the one flag byte per lane and its ballot):
+// the tail ranks exchange busy and idle envs; fidx = the env's byte in a flag
+// buffer (-1 outside mode 2).
+__device__ __forceinline__ int lo_swap_env(const EnvParams &p, int q, int &fidx) {
+  const uint32_t w = (uint32_t)p.pad0;
+  fidx = -1;
+  if (lo_mode(w) == kLoIdleLast) {
+    const int C = lo_chunks(p.N), T = lo_T(w), nr = lo_nr(w);
+    int r = q / C;
+    const int c = q - r * C;
+    if (lo_in_tail(r, T, nr)) {
+      const int lane = lane_id();
+      const uint8_t GLBP *line = gptr(lo_flags(p, lo_parity(w))) + (int64_t)c * kLoChunk;
+      const bool in = lane < 2 * T;
+      const uint8_t f = in ? line[lo_lane_rank(lane, T, nr)] : (uint8_t)0;
+      const uint32_t busy = (uint32_t)ballot(in && f != 0);
+      r = uni(lo_partner(busy, T, nr, lo_parity(w), r));
+      q = r * C + c;
+    }
+    fidx = c * kLoChunk + r;
+  }
+  return q;
+}
+// The env's flag for the launch after this one: 0 where the header written
+// back (hint word ph, clock t) meets idle_step's header terms, else 1.
+__device__ __forceinline__ void lo_store_flag(const EnvParams &p, int fidx, uint64_t ph, int64_t t) {
+  if (fidx < 0) return;
+  const uint32_t nf = (uint32_t)ph;
+  const bool q1 = (ph >> 62) & 1u, q2 = (ph >> 60) & 1u;
+  const bool idle = (ph >> 63) && q1 != q2 && (ph & 0x0FFFFFFF00000000ull) == 0 && nf != 0u &&
+                    (int32_t)(nf - (uint32_t)t) > 1;
+  gptr(lo_flags(p, lo_parity((uint32_t)p.pad0) ^ 1))[fidx] = (uint8_t)!idle;
+}
+
 // ---- the idle step of a per-step heuristic launch -------------------------
 // A per-step launch whose header says that the step changes nothing of the
 // env but its clock: the heuristic is skipped (EnvHdr::pad bit 62 or 60, see
@@ -628,7 +669,7 @@ __device__ __forceinline__ bool idle_step(const EnvParams &p, const StepOut &o, 
 template <int VPT>
 __device__ __forceinline__ void idle_body(const EnvParams &p, const StepOut &o, const Lds &L,
                                           const float LDSP *fcent, int e,
-                                          const uint32_t (&wa)[VPT]) {
+                                          const uint32_t (&wa)[VPT], int fidx) {
   const int lane = lane_id();
   const int V = p.V;
   EnvHdr LDSP *H = L.hdr;
@@ -660,6 +701,7 @@ __device__ __forceinline__ void idle_body(const EnvParams &p, const StepOut &o, 
     H->timestep = ts + 1;
     H->total_requests += a;
     H->dropped += a;
+    lo_store_flag(p, fidx, ph, ts + 1);
   }
   wsync();
   if (lane < 32)
@@ -685,8 +727,12 @@ __device__ __forceinline__ void env_body(const EnvParams &p, const StepOut &o) {
 #endif
   const int lane = lane_id();
   const int wid = threadIdx.x >> 6;
-  const int e_raw = uni(blockIdx.x * kEnvWavesPerBlock + wid);
-  const int e = e_raw < p.N ? e_raw : p.N - 1;  // tail waves load a valid env, then leave
+  // per-step launches take their env from the launch-order layer: the
+  // dispatch position here, the heuristic kernel's exchange behind the header load
+  int fidx = -1;
+  int e_raw = uni(blockIdx.x * kEnvWavesPerBlock + wid);
+  if constexpr (ONE) e_raw = uni(lo_position((uint32_t)p.pad0, p.N, e_raw));
+  int e = e_raw < p.N ? e_raw : p.N - 1;  // tail waves load a valid env, then leave
   char LDSP *base = (char LDSP *)lds + wid * p.lds_wave_bytes;
   const Lds L = make_lds(p, base);
   const int V = p.V, P = p.P;
@@ -699,7 +745,17 @@ __device__ __forceinline__ void env_body(const EnvParams &p, const StepOut &o) {
   // critical path starts at their latency (burst launches -1.1-1.6 %,
   // profiles/r04_prio_prologue_ab.log)
   __builtin_amdgcn_s_setprio(2);
-  const uint64_t hv = gptr(reinterpret_cast<const uint64_t *>(p.hdr + e))[lane & 31];
+  uint64_t hv = gptr(reinterpret_cast<const uint64_t *>(p.hdr + e))[lane & 31];
+  // idle envs last: the flags are read while the position's own header is in
+  // flight (the exchange then costs a wave that keeps its env no load latency
+  // of its own); a wave that takes another env loads that header instead
+  if constexpr (ONE && !EXT && SRC != kSrcTrace) {
+    const int e2 = uni(lo_swap_env(p, e, fidx));
+    if (e2 != e) {
+      e = e_raw = e2;
+      hv = gptr(reinterpret_cast<const uint64_t *>(p.hdr + e))[lane & 31];
+    }
+  }
   // Poisson constants for the block's LDS copy (issued before the state loads,
   // so waiting for them never waits on the state): the env's own pair, one
   // env per workgroup (e is wave-uniform: scalar address arithmetic)
@@ -800,7 +856,7 @@ __device__ __forceinline__ void env_body(const EnvParams &p, const StepOut &o) {
   // Traced envs keep the general path.
   if constexpr (ONE && !EXT && SRC != kSrcTrace) {
   if (idle_step(p, o, L)) {
-    idle_body<VPT>(p, o, L, (const float LDSP *)T.fcent, e, wa);
+    idle_body<VPT>(p, o, L, (const float LDSP *)T.fcent, e, wa, fidx);
 #ifdef VMP_STAMPS
     if (p.stamps && lane == 0) stamp_idle(p.stamps + (int64_t)e * kStamps, t_start, rt_start);
 #endif
@@ -976,7 +1032,10 @@ __device__ __forceinline__ void env_body(const EnvParams &p, const StepOut &o) {
       hint |= ((uint64_t)(qkind == 1) << 62) | ((uint64_t)(qkind == 2) << 60) |
               ((uint64_t)has_ex << 61);
       wsync();
-      if (lane == 0) L.hdr->pad = hint;
+      if (lane == 0) {
+        L.hdr->pad = hint;
+        if constexpr (ONE && !EXT && SRC != kSrcTrace) lo_store_flag(p, fidx, hint, L.hdr->timestep);
+      }
       wsync();
     }
     if (lane < 32)

@@ -37,6 +37,7 @@ __global__ void k_counters(EnvParams p, int64_t *ctr, double *st);
 __global__ void k_target_means(EnvParams p);
 __global__ void k_mask_bool(int64_t rows, int A, int W, const uint32_t *bits, uint8_t *mask);
 __global__ void k_act_obs(int P, int V, int policy, const float *obs, int32_t *act);
+__global__ void k_launch_map(EnvParams p, int32_t *env_of_block);
 
 // k_env_big: one workgroup per env (kBigNT threads, big_spt slots per thread:
 // vmp_carve.h); its launchers live with the kernel (vmp_kernels.hip)

@@ -27,7 +27,7 @@ EXPORTS = (
     "vmp_series_enable", "vmp_series_info", "vmp_series_read",
     "vmp_snapshot_bytes", "vmp_snapshot", "vmp_restore",
     "vmp_debug_fail_alloc", "vmp_debug_live_allocs", "vmp_debug_stamps", "vmp_debug_occupancy",
-    "vmp_debug_quiet_violations",
+    "vmp_debug_quiet_violations", "vmp_debug_launch_order", "vmp_debug_launch_map",
 )
 
 
@@ -139,6 +139,8 @@ def lib():
         "vmp_debug_stamps": (ctypes.c_int, [P, P]),
         "vmp_debug_occupancy": (ctypes.c_int, [P, P, P]),
         "vmp_debug_quiet_violations": (ctypes.c_int, [P]),
+        "vmp_debug_launch_order": (ctypes.c_int, [P, i32]),
+        "vmp_debug_launch_map": (ctypes.c_int, [P, P, P]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name, None)
