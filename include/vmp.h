@@ -323,6 +323,36 @@ int vmp_snapshot_bytes(const vmp_handle *h, int64_t *bytes);
 int vmp_snapshot(vmp_handle *h, void *dst);
 int vmp_restore(vmp_handle *h, const void *src);
 
+/* Branch env states between handles on the device: "what would happen from THIS state if ...".
+ * For every dst env i with 0 <= src_of_dst[i] < src.n_env, dst env i receives the complete state
+ * of that src env: its header (streams, sequence bases, timestep, counters, stats and the step
+ * hint word, verbatim: the hints describe the state they travel with), its PM row and its whole
+ * VM row, the padded words behind slot V included, so the env's rows of a vmp_snapshot are equal
+ * byte for byte. -1, and any other value outside the range, keeps dst env i untouched; such a
+ * value is never used as an index (the map lives on the device: the host does not see it).
+ *  src_of_dst: device int32[dst.n_env]
+ *  seeds:      device int64[dst.n_env], nullable. Where seeds[i] >= 0 on a copied env, its four
+ *              streams become what vmp_reset writes for reset(seed = seeds[i]) (stream k = PCG64
+ *              of seeds[i] + k, the sequence bases the fresh states of streams 1 and 2) and
+ *              everything else stays the copied state; seeds[i] < 0 keeps the copied streams.
+ * Not copied: eval mode, the per-env workload, the trace and its map, the launch-order flags
+ * (stale flags cost speed only). A dst env continues under dst's own workload or trace at the
+ * copied timestep. The env counts may differ.
+ * VMP_EINVAL: a null handle or map; handles of different pms, vms or action count, of configs
+ * that differ in anything but the seed (the check of vmp_restore), or on different devices.
+ * VMP_ESTATE: one handle has a trace and the other has none. Both handles stay usable.
+ * dst == src is allowed and correct for any map (overlaps, swaps, one env to all): the call then
+ * reads a staging copy owned by the handle, allocated on the first such call (VMP_EOOM if that
+ * fails, the handle unchanged) and freed by vmp_destroy.
+ * Stream-ordered on dst's stream; ordering against work queued on src's stream is the caller's
+ * job (the Python layer binds both to one stream). With dst != src the call allocates nothing
+ * and never synchronises, so it may be captured in a graph; the map and seeds are read on the
+ * device at replay. The one exception: on a dst with the recorder, the request log or the time
+ * series on, the first call allocates an n_env-byte mask, so make one call before capturing.
+ * Those observers restart for exactly the overwritten dst envs, from the new state, as after
+ * vmp_reset with their mask; the observers of kept envs continue. (ABI 14, additive) */
+int vmp_branch(vmp_handle *dst, vmp_handle *src, const int32_t *src_of_dst, const int64_t *seeds);
+
 /* PPOAgent.update GAE (ppo.py:232-243) over T steps x N envs, reverse scan:
  *  delta = r + (1-d)*gamma*v' - v;  g = delta + (1-d)*gamma*lambda*g.
  * All device f32 [T][N] (done as f32 0/1); adv and ret are outputs. */

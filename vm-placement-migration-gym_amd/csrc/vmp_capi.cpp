@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/vmp.h"
+#include "vmp_branch.h"
 #include "vmp_carve.h"
 #include "vmp_host.h"
 #include "vmp_kernels.h"
@@ -81,6 +82,10 @@ struct vmp_handle {
   // two flag buffers lie behind hdr. None of it is part of a snapshot.
   uint32_t lo_count;
   int32_t lo_mode, lo_div;
+  // vmp_branch: the staging copy of hdr | pm | vmw for dst == src, and the mask of
+  // the overwritten envs that restarts the observers; each allocated on first use
+  uint8_t *br_stage;
+  uint8_t *br_mask;
 };
 
 namespace {
@@ -344,7 +349,7 @@ int vmp_destroy(vmp_handle *h) {
   for (void *q : {(void *)h->vmw, (void *)h->pm, (void *)h->hdr, (void *)h->lg_arr, (void *)h->lg_svc,
                   (void *)h->scratch_bits, (void *)h->pois_dev, (void *)h->jump_dev, (void *)h->bigscr,
                   (void *)h->stamps, (void *)h->pois_env, (void *)h->lg_shared, (void *)h->tr_tab,
-                  (void *)h->tr_data})
+                  (void *)h->tr_data, (void *)h->br_stage, (void *)h->br_mask})
     dev_free(q);
   std::free(h->wl);
   std::free(h->wl_rec);
@@ -1104,6 +1109,80 @@ int vmp_restore(vmp_handle *h, const void *src) {
   if (h->rq_on)  // nor is the log
     if (const int rc = reqlog_init(h, nullptr)) return rc;
   return h->sr_on ? series_init(h, nullptr) : VMP_OK;  // nor is the time series
+}
+
+// ---- branch: env states between handles on the device ----
+// One gather launch (vmp_branch.hip) on dst's stream. dst == src reads a staging
+// copy of the three arrays made on the same stream just before, so any map is
+// correct in place. The observers of the overwritten envs restart through the
+// mask the kernel derives from the map.
+namespace {
+BranchSide branch_side(const vmp_handle *h) {
+  BranchSide s;
+  std::memset(&s, 0, sizeof(s));
+  s.P = h->P, s.V = h->V, s.A = h->A;
+  s.device = h->device;
+  s.traced = h->tr_tab ? 1 : 0;
+  s.cfg = h->cfg;
+  return s;
+}
+}  // namespace
+
+int vmp_branch(vmp_handle *dst, vmp_handle *src, const int32_t *src_of_dst, const int64_t *seeds) {
+  if (!dst || !src || !src_of_dst) return fail(VMP_EINVAL, "vmp_branch: null handle or map");
+  const BranchSide ds = branch_side(dst), ss = branch_side(src);
+  const char *why = nullptr;
+  if (const int rc = branch_check(&ds, &ss, src_of_dst, &why)) return fail(rc, why);
+  const BranchGeom g = branch_geom(dst->P, vm_pitch(dst->V));
+  if ((int64_t)dst->N * g.chunks > 0x7fffffffLL) return fail(VMP_EINVAL, "vmp_branch: too many envs for one launch");
+  const SnapLayout l(src);  // sizes of src's three arrays
+  const bool observed = dst->rec_on || dst->rq_on || dst->sr_on;
+  if (dst == src && !dst->br_stage) {
+    const hipError_t e = dev_malloc(&dst->br_stage, l.nh + l.np + l.nv);
+    if (e != hipSuccess)
+      return fail(e == hipErrorOutOfMemory ? VMP_EOOM : VMP_EDEVICE,
+                  std::string("vmp_branch staging: ") + hipGetErrorString(e));
+  }
+  if (observed && !dst->br_mask) {
+    const hipError_t e = dev_malloc(&dst->br_mask, (size_t)dst->N);
+    if (e != hipSuccess)
+      return fail(e == hipErrorOutOfMemory ? VMP_EOOM : VMP_EDEVICE,
+                  std::string("vmp_branch mask: ") + hipGetErrorString(e));
+  }
+  BranchArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.src_hdr = reinterpret_cast<const uint4 *>(src->hdr);
+  a.src_pm = reinterpret_cast<const uint4 *>(src->pm);
+  a.src_vmw = reinterpret_cast<const uint4 *>(src->vmw);
+  if (dst == src) {
+    uint8_t *st = dst->br_stage;
+    HIP_TRY(hipMemcpyAsync(st, src->hdr, l.nh, hipMemcpyDeviceToDevice, dst->stream));
+    HIP_TRY(hipMemcpyAsync(st + l.nh, src->pm, l.np, hipMemcpyDeviceToDevice, dst->stream));
+    HIP_TRY(hipMemcpyAsync(st + l.nh + l.np, src->vmw, l.nv, hipMemcpyDeviceToDevice, dst->stream));
+    a.src_hdr = reinterpret_cast<const uint4 *>(st);
+    a.src_pm = reinterpret_cast<const uint4 *>(st + l.nh);
+    a.src_vmw = reinterpret_cast<const uint4 *>(st + l.nh + l.np);
+  }
+  a.dst_hdr = reinterpret_cast<uint4 *>(dst->hdr);
+  a.dst_pm = reinterpret_cast<uint4 *>(dst->pm);
+  a.dst_vmw = reinterpret_cast<uint4 *>(dst->vmw);
+  a.src_of_dst = src_of_dst;
+  a.seeds = seeds;
+  a.mask = observed ? dst->br_mask : nullptr;
+  a.src_n = src->N;
+  a.dst_n = dst->N;
+  a.pm_units = (int32_t)g.pm_units;
+  a.vm_units = (int32_t)g.vm_units;
+  a.units = (int32_t)g.units;
+  a.chunks = (int32_t)g.chunks;
+  hipLaunchKernelGGL(k_branch, dim3((unsigned)((int64_t)dst->N * g.chunks)), dim3(kBranchThreads), 0,
+                     dst->stream, a);
+  if (const int rc = launched()) return rc;
+  if (dst->rec_on)  // the observers of the overwritten envs restart from the new state
+    if (const int rc = record_init(dst, dst->br_mask)) return rc;
+  if (dst->rq_on)
+    if (const int rc = reqlog_init(dst, dst->br_mask)) return rc;
+  return dst->sr_on ? series_init(dst, dst->br_mask) : VMP_OK;
 }
 
 int64_t vmp_debug_live_allocs(void) { return g_live.load(); }

@@ -25,7 +25,7 @@ EXPORTS = (
     "vmp_actor_mlp_f32", "vmp_actor_mlp_head_f32", "vmp_step_mask", "vmp_record_enable",
     "vmp_record_read", "vmp_reqlog_enable", "vmp_reqlog_info", "vmp_reqlog_read",
     "vmp_series_enable", "vmp_series_info", "vmp_series_read",
-    "vmp_snapshot_bytes", "vmp_snapshot", "vmp_restore",
+    "vmp_snapshot_bytes", "vmp_snapshot", "vmp_restore", "vmp_branch",
     "vmp_debug_fail_alloc", "vmp_debug_live_allocs", "vmp_debug_stamps", "vmp_debug_occupancy",
     "vmp_debug_quiet_violations", "vmp_debug_launch_order", "vmp_debug_launch_map",
 )
@@ -134,6 +134,7 @@ def lib():
         "vmp_snapshot_bytes": (ctypes.c_int, [P, P]),
         "vmp_snapshot": (ctypes.c_int, [P, P]),
         "vmp_restore": (ctypes.c_int, [P, P]),
+        "vmp_branch": (ctypes.c_int, [P, P, P, P]),
         "vmp_debug_fail_alloc": (ctypes.c_int, [i32]),
         "vmp_debug_live_allocs": (ctypes.c_int64, []),
         "vmp_debug_stamps": (ctypes.c_int, [P, P]),
@@ -147,7 +148,8 @@ def lib():
         if f is None and name.startswith("vmp_debug_"):
             continue  # diagnostics an older build may lack
         if f is None:
-            raise VmpError(f"libvmp lacks {name}")
+            raise VmpError(f"libvmp lacks {name}: {LIB_PATH} was built from older sources "
+                           "(ABI 14 gained entry points without a new number); rebuild it")
         f.restype, f.argtypes = res, args
     if L.vmp_abi_version() != 14:
         raise VmpError("libvmp ABI mismatch")

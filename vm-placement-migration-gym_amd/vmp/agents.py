@@ -181,3 +181,147 @@ class BestFitAgent(_HeuristicAgent):
     """bestfit.py:21-40: feasible PM with the largest f32 cpu+mem, numpy scalar
     introsort tie order."""
     POLICY = "bestfit"
+
+
+def choose_candidates(returns):
+    """The rollout agent's choice: returns [n, C] (any float tensor, CPU or
+    device) -> int64 [n], the candidate with the largest return of each row,
+    the LOWEST index among equal ones. A candidate wins only by being strictly
+    greater than every earlier one, so a NaN return never wins against a
+    number before it. A fixed chain of comparisons: no host round trip."""
+    import torch
+    if returns.dim() != 2 or returns.shape[1] < 1:
+        raise ValueError("returns must be [n, C] with C >= 1")
+    best = returns[:, 0]
+    idx = torch.zeros(returns.shape[0], dtype=torch.int64, device=returns.device)
+    for c in range(1, returns.shape[1]):
+        better = returns[:, c] > best
+        idx = torch.where(better, torch.full_like(idx, c), idx)
+        best = torch.where(better, returns[:, c], best)
+    return idx
+
+
+class RolloutAgent:
+    """A rollout (policy-switching) agent between the heuristics and PPO: at
+    every step each env tries every candidate action on copies of its own
+    state, lets the `base` heuristic play `horizon` further steps, and takes
+    the candidate with the best mean return.
+
+    env: a BatchedVmEnv (or a vmp.VmEnv) of n envs. candidates: "firstfit" /
+    "bestfit" (the heuristic's action on the current state) and "wait" (every
+    VM's current placement: nothing is placed or moved this step). The agent
+    holds a scratch BatchedVmEnv of n * C * futures envs of the same config,
+    given the parent's per-env workload rows once, or the parent's traces and
+    map when the parent is traced; a trace has one future, so futures is then 1.
+    Scratch env (i * C + c) * M + m is env i's future m under candidate c.
+
+    step():
+      1. the scratch envs take their env's state (BatchedVmEnv.branch); on an
+         RNG workload future m of env i at the agent's step t gets fresh
+         streams from the counter-based seed
+         seed + 4 * ((t * n + i) * M + m), the same for every candidate
+         (common random numbers: candidates are compared on equal arrivals);
+      2. candidate c's action is applied as one external step;
+      3. rollout(base, horizon);
+      4. the rewards are added in step order, the first step's included, then
+         averaged over the M futures;
+      5. choose_candidates: argmax per env, ties to the lowest index;
+      6. the real env steps with that candidate's action.
+    Everything runs on the device on the current stream; nothing is read back."""
+    CANDIDATES = ("firstfit", "bestfit", "wait")
+
+    def __init__(self, env, candidates=("firstfit", "bestfit", "wait"), horizon=10, futures=1,
+                 base="firstfit", seed=None):
+        import torch
+
+        from . import _lib
+        from .batched import BatchedVmEnv
+        b = batched_env(env)
+        candidates = tuple(candidates)
+        if not candidates or any(c not in self.CANDIDATES for c in candidates):
+            raise ValueError(f"candidates must be a non-empty choice of {self.CANDIDATES}")
+        if base not in _lib.POLICIES:
+            raise ValueError(f"base must be one of {tuple(_lib.POLICIES)}")
+        if int(horizon) < 0 or int(futures) < 1:
+            raise ValueError("horizon must be >= 0 and futures >= 1")
+        self.env, self.b = env, b
+        self.candidates, self.base, self.K = candidates, base, int(horizon)
+        self.traced = b._traces is not None
+        self.C, self.M = len(candidates), 1 if self.traced else int(futures)
+        n, per = b.n_envs, self.C * self.M
+        self.seed = int(b.config.seed if seed is None else seed)
+        if self.seed < 0:
+            raise ValueError("seed must be non-negative")
+        self.t = 0
+        self.scratch = BatchedVmEnv(b.config, n * per, device=b.device)
+        try:
+            if self.traced:
+                traces, tmap = b._traces
+                self.scratch.set_trace(traces, np.repeat(tmap, per))
+            else:
+                a, s = b.workload()
+                if np.any(a != float(b.config.arrival_rate)) or np.any(s != float(b.config.service_length)):
+                    self.scratch.set_workload(np.repeat(a, per), np.repeat(s, per))
+        except Exception:
+            self.scratch.close()
+            raise
+        dev = b.device
+        j = torch.arange(n * per, device=dev)
+        self._src = (j // per).to(torch.int32)
+        # (i * M + m) of every scratch env: the same for all candidates
+        self._future = (j // per) * self.M + j % self.M
+        self._rows = torch.arange(n, device=dev)
+
+    def close(self):
+        self.scratch.close()
+
+    def candidate_actions(self):
+        """int32 [n, C, V]: every candidate's action on the env's current state."""
+        import torch
+        acts = []
+        for c in self.candidates:
+            if c == "wait":
+                acts.append(self.b.state()["vm_placement"].to(torch.int32))
+            else:
+                acts.append(self.b.heuristic_act(c))
+        return torch.stack(acts, dim=1)
+
+    def future_seeds(self):
+        """int64 [n * C * M] seeds of this step's futures, None on a traced env."""
+        if self.traced:
+            return None
+        n = self.b.n_envs
+        s = self.seed + 4 * (self.t * n * self.M + self._future)
+        return s & ((1 << 62) - 1)
+
+    def returns(self, acts):
+        """f64 [n, C]: the mean over the futures of the summed rewards of
+        candidate c's action followed by `horizon` steps of the base policy."""
+        n, per, sc = self.b.n_envs, self.C * self.M, self.scratch
+        if sc.eval_mode != self.b.eval_mode:  # the termination limit is no part of the state
+            sc.eval(self.b.eval_mode)
+        sc.branch(self.b, self._src, self.future_seeds())
+        a = acts.unsqueeze(2).expand(n, self.C, self.M, self.b.V).reshape(n * per, self.b.V)
+        _, total, _, _ = sc.step(a.contiguous(), want_valid=False, bool_done=False)
+        if self.K:
+            rew, _ = sc.rollout(self.base, self.K)
+            for k in range(self.K):
+                total = total + rew[k]
+        total = total.view(n, self.C, self.M)
+        ret = total[:, :, 0]
+        for m in range(1, self.M):
+            ret = ret + total[:, :, m]
+        return ret / self.M if self.M > 1 else ret
+
+    def act(self):
+        """(actions int32 [n, V], choice int64 [n]) for the env's current state."""
+        acts = self.candidate_actions()
+        choice = choose_candidates(self.returns(acts))
+        self.t += 1
+        return acts[self._rows, choice], choice
+
+    def step(self):
+        """One agent step of every env -> (obs, reward, done, valid, choice)."""
+        action, choice = self.act()
+        obs, reward, done, valid = self.b.step(action)
+        return obs, reward, done, valid, choice

@@ -53,6 +53,7 @@ class BatchedVmEnv:
                                    seeds.ctypes.data_as(ctypes.c_void_p), self.device.index,
                                    ctypes.byref(h)))
         self._h = h
+        self._traces = None
         if arrival_rate is not None or service_length is not None:
             try:
                 self.set_workload(arrival_rate, service_length)
@@ -152,12 +153,15 @@ class BatchedVmEnv:
         pm = None if m is None else m.ctypes.data_as(ctypes.c_void_p)
         with torch.cuda.device(self.device):
             check(lib().vmp_set_trace(h, len(traces), ctypes.cast(arr, ctypes.c_void_p), pm))
+        # kept for an env that is to replay the same ones (vmp.agents.RolloutAgent)
+        self._traces = (traces, np.zeros(self.n_envs, np.int32) if m is None else m.copy())
 
     def clear_trace(self):
         """Back to the RNG workload (the per-env one if the env has it), the
         streams where they stood (vmp_clear_trace)."""
         with torch.cuda.device(self.device):
             check(lib().vmp_clear_trace(self._bind()))
+        self._traces = None
 
     def trace_info(self):
         """None without a trace, else dict(n_traces, trace_of_env int32 [n_envs],
@@ -454,3 +458,50 @@ class BatchedVmEnv:
             raise ValueError(f"snapshot holds {s.numel()} bytes, this env needs {n.value}")
         check(lib().vmp_restore(h, ptr(s)))
         torch.cuda.current_stream(self.device).synchronize()  # s may be a temporary copy
+
+    # ------------------------------------------------------------ branching
+    def _branch_arg(self, x, dtype, name, lo=None, hi=None):
+        """index / seeds of `branch` as a contiguous device tensor [n_envs].
+        Host values are range-checked here; a device tensor is taken as it is
+        (the kernel keeps an env whose entry is out of range)."""
+        if isinstance(x, torch.Tensor) and x.is_cuda:
+            if x.numel() != self.n_envs:
+                raise ValueError(f"{name} must have n_envs = {self.n_envs} entries")
+            if x.device != self.device:
+                raise ValueError(f"{name} lives on {x.device}, the env on {self.device}")
+            return x.reshape(-1).to(dtype).contiguous()
+        a = np.asarray(x.numpy() if isinstance(x, torch.Tensor) else x)
+        if a.shape != (self.n_envs,):
+            raise ValueError(f"{name} must have n_envs = {self.n_envs} entries")
+        if a.dtype.kind not in "iu":
+            raise ValueError(f"{name} must be integers")
+        a = a.astype(np.int64)
+        if lo is not None and (a.min() < lo or a.max() >= hi):
+            raise ValueError(f"{name} entries must be in [{lo}, {hi})")
+        return torch.as_tensor(a, device=self.device).to(dtype)
+
+    def branch(self, src, index, seeds=None):
+        """Copy env states on the device (vmp_branch): env i of this env takes
+        the complete state of env index[i] of `src` (streams, counters, PMs,
+        VMs; bit for bit, so it continues exactly as that env would), -1 keeps
+        env i as it is. `src` is a BatchedVmEnv of the same config (the seed
+        and n_envs may differ) or this env itself: any map is correct in
+        place. seeds (optional): where seeds[i] >= 0 the copied env gets the
+        four RNG streams of reset(seed=seeds[i]) instead, i.e. its own future
+        from the copied state; negative entries keep the copied streams.
+        index / seeds: device tensors, host arrays or lists of n_envs entries;
+        host values are range-checked (ValueError), device tensors are read by
+        the kernel only, which keeps an env whose entry is out of range. Eval
+        mode, the per-env workload and the trace stay this env's own. The
+        recorder, request log and series restart for the overwritten envs.
+        No host synchronisation; with src is not self it can be captured in a
+        graph (tensor arguments are then read at every replay)."""
+        if not isinstance(src, BatchedVmEnv):
+            raise ValueError("src must be a BatchedVmEnv")
+        if src.device != self.device:
+            raise ValueError("src lives on another device")
+        hd = self._bind()
+        hs = src._bind()
+        m = self._branch_arg(index, torch.int32, "index", -1, src.n_envs)
+        s = None if seeds is None else self._branch_arg(seeds, torch.int64, "seeds")
+        check(lib().vmp_branch(hd, hs, ptr(m), ptr(s)))
