@@ -35,7 +35,8 @@ __device__ __forceinline__ int64_t heuristic_apply(const EnvParams &p, const Lds
                                                    const Tables &T, uint32_t (&wa)[VPT],
                                                    int policy, int32_t *act_out,
                                                    uint8_t *valid_out, bool quiet, int qkind,
-                                                   bool &fit_any STAMP_PARAMS) {
+                                                   bool &fit_any, bool count_wait,
+                                                   int &n_wait STAMP_PARAMS) {
   const int lane = lane_id();
   const int P = p.P, WAIT = p.P;
   const bool bf = policy == 1;
@@ -43,6 +44,9 @@ __device__ __forceinline__ int64_t heuristic_apply(const EnvParams &p, const Lds
 #pragma unroll
   for (int s = 0; s < VPT; s++)
     if (w_pl(wa[s]) == WAIT) pend |= 1u << s;
+  // count_wait (a launch's first step): the number of waiting VMs before the
+  // action phase, the start of the n_w that env_tail carries
+  if (count_wait) n_wait = (int)wave_sum32((uint32_t)__popc(pend));
   uint32_t won = 0, bad = 0;
   int64_t n_place = 0;
   fit_any = false;
@@ -195,9 +199,10 @@ template <int VPT>
 __device__ __forceinline__ void external_apply(const EnvParams &p, const Lds &L, const Tables &T,
                                                uint32_t (&wa)[VPT], const int32_t *act_row,
                                                uint8_t *valid_out, int64_t &n_place,
-                                               int64_t &n_susp) {
+                                               int64_t &n_susp, int &n_wait) {
   const int lane = lane_id();
   const int P = p.P, WAIT = p.P;
+  int n_wait0 = 0;
   // all action loads issued at once, unconditionally (clamped index) and
   // through the global address space: one wait for all of them instead of a
   // conditional load + wait per slot row
@@ -212,6 +217,9 @@ __device__ __forceinline__ void external_apply(const EnvParams &p, const Lds &L,
     const bool in = live(wa[s]);
     const int c = w_pl(wa[s]);
     const int t = in ? tv[s] : c;
+    // the waiting VMs before the action phase (a pad word's placement is
+    // kPad); a scalar count: this kernel has no VGPR to spare at VPT 1
+    n_wait0 += __popcll(ballot(c == WAIT));
     const bool isplace = in && c == WAIT && t >= 0 && t < P;
     const bool issusp = in && c < P && t == WAIT;
     uint64_t evm = ballot(isplace || issusp);
@@ -254,6 +262,7 @@ __device__ __forceinline__ void external_apply(const EnvParams &p, const Lds &L,
     if (ok && t != c && in) wa[s] = (wa[s] & 0xFFFF0000u) | (uint32_t)t;
     if (valid_out && in) gptr(valid_out)[v] = (uint8_t)ok;
   }
+  n_wait = n_wait0;
 }
 
 // Everything of step() after the action phase: _run_vms, _accept_vm_requests,
@@ -263,13 +272,19 @@ __device__ __forceinline__ void external_apply(const EnvParams &p, const Lds &L,
 // waiting: remaining <= 1, i.e. placed now it finishes now), accepted words are
 // stored at once through `vmo`, and the caller fixes the finish keys of placed /
 // suspended VMs in memory; rem[] is then unused.
-template <int VPT, bool LAZY, int SRC>
+// The VM counts of the stats come from the step's events, not from a sweep of
+// the slot words: n_w (in: the waiting VMs before this step's action phase;
+// out: after the step) moves by the n_susp suspensions, the n_place accepted
+// placements and the k accepted requests, and null_left (out) = n_null - k is
+// the number of NULL slots the step leaves, so V - null_left VMs exist.
+template <int VPT, bool LAZY, int SRC, bool EXTK>
 __device__ __forceinline__ double env_tail(const EnvParams &p, const Lds &L, const Tables &T,
                                            uint32_t (&wa)[VPT], uint32_t (&rem)[VPT],
                                            uint32_t run0, uint32_t fb, uint32_t &dirty,
-                                           uint32_t *vmo, int kstep, bool ext,
-                                           bool quiet_in, bool &terminated, bool &calm,
-                                           bool &has_ex, int e STAMP_PARAMS) {
+                                           uint32_t *vmo, int kstep,
+                                           bool quiet_in, int64_t n_place, int64_t n_susp,
+                                           int &n_w, int &null_left, bool &terminated,
+                                           bool &calm, bool &has_ex, int e STAMP_PARAMS) {
   const int lane = lane_id();
   const int P = p.P, WAIT = p.P, NUL = p.P + 1;
   EnvHdr LDSP *H = L.hdr;
@@ -282,11 +297,28 @@ __device__ __forceinline__ double env_tail(const EnvParams &p, const Lds &L, con
   // action phase) tells which words switch representation.
   const uint32_t t32 = (uint32_t)H->timestep;
   int64_t n_term = 0;
+  // LAZY: the running slots after the action phase as a mask. The step's only
+  // WAIT -> PM / PM -> WAIT moves are its n_place accepted placements and
+  // n_susp suspensions, so without either the mask is run0 and no word
+  // switches representation; and where no lane has a finish bit among its
+  // running slots (one ballot) no VM finishes, and the per-slot loop is skipped.
+  uint32_t run1 = run0;
+  bool any_fin = true;
+  if (LAZY) {
+    if (n_place != 0 || n_susp != 0) {
+      run1 = 0;
+#pragma unroll
+      for (int s = 0; s < VPT; s++) run1 |= (uint32_t)(w_pl(wa[s]) < P) << s;
+      dirty |= run1 ^ run0;
+    }
+    any_fin = ballot((fb & run1) != 0u) != 0;
+  }
+  if (any_fin) {
 #pragma unroll
   for (int s = 0; s < VPT; s++) {
-    const bool running = w_pl(wa[s]) < P;
-    if (running != (bool)((run0 >> s) & 1u)) {
-      if (!LAZY) rem[s] = running ? rem[s] + t32 : rem[s] - t32;  // placed : suspended
+    const bool running = LAZY ? (bool)((run1 >> s) & 1u) : w_pl(wa[s]) < P;
+    if (!LAZY && running != (bool)((run0 >> s) & 1u)) {
+      rem[s] = running ? rem[s] + t32 : rem[s] - t32;  // placed : suspended
       dirty |= 1u << s;
     }
     // remaining r = F - t: decrement if r > 0, finish if it reaches 0
@@ -316,10 +348,11 @@ __device__ __forceinline__ double env_tail(const EnvParams &p, const Lds &L, con
       dirty |= 1u << s;
     }
   }
+  }
   // precision clamp (env.py:267-268): every stored load is 0 or >= 1e-7 after
   // the previous step's clamp and placements only add, so only a free or a
   // suspension (external actions) can leave a value below 1e-7
-  if (n_term > 0 || ext)
+  if (n_term > 0 || n_susp > 0)
     for (int i = lane; i < P; i += 64) {
       if (L.cpu[i] < 1e-7) L.cpu[i] = 0;
       if (L.mem[i] < 1e-7) L.mem[i] = 0;
@@ -405,26 +438,42 @@ __device__ __forceinline__ double env_tail(const EnvParams &p, const Lds &L, con
   // eval-mode info; for wr/ut they are derived on demand from the stored state
   // by k_target_means (vmp_get_stats), so the step skips the two V-long sums.
   const bool kl = p.reward == 2;
-  int n_ex = 0, n_w = 0;
+  // The counts, from the step's events. n_null is exact: the NULL list above
+  // was built, or no_null proved that there is no NULL slot. Every live slot
+  // holds a VM or is NULL, so n_ex = V - (n_null - k), on the V live slots and
+  // not the padded rows. A waiting VM leaves WAIT only by an accepted placement
+  // and a VM enters WAIT only by a suspension or as an accepted request (a VM
+  // placed and finished in this step was waiting before and is NULL after).
+  null_left = n_null - (int)k;
+  n_w += (int)n_susp - (int)n_place + (int)k;
+  int n_ex = p.V - null_left;
+  // (0 <= null_left <= V <= 64 VPT: the range the popcounts of a sweep made
+  // plain to the compiler; without it the pairwise sums below are compiled
+  // for any n, at 30-40 more VGPRs in the trace kernels)
+  __builtin_assume(n_ex >= 0 && n_ex <= VPT * 64);
   // wr after a quiet step in which nothing finished, arrived or was placed:
   // the VM set is the previous step's, so is its waiting ratio (stored in the
   // header) and whether any VM exists (has_ex: carried by the caller, from
-  // EnvHdr::pad bit 61 at the launch's start)
+  // EnvHdr::pad bit 61 at the launch's start); n_w stays as it was
   const bool same_vms = p.reward == 0 && quiet_in && n_term == 0 && k == 0;
-  if (!same_vms) {
+  // kl: the existing VMs' sizes, compressed in slot order. EXTK (the
+  // external-action kernels) keeps the sweep's own n_ex, the same number: with
+  // the derived one k_env_ext<1> (128 VGPRs at 4 waves per SIMD) spills VGPRs
+  // and k_env_ext_tr<8> needs 15 more
+  if (EXTK || kl) {
+    int off = 0;
 #pragma unroll
     for (int s = 0; s < VPT; s++) {
-      const int c = w_pl(wa[s]);
-      const bool ex = c <= WAIT;
+      const bool ex = w_pl(wa[s]) <= WAIT;
       const uint64_t em = ballot(ex);
       if (kl && ex) {
-        const int rk = n_ex + below(em, lane);
+        const int rk = off + below(em, lane);
         L.ccomp[rk] = (uint8_t)w_cc(wa[s]);
         L.mcomp[rk] = (uint8_t)w_cm(wa[s]);
       }
-      n_ex += __popcll(em);
-      n_w += __popcll(ballot(c == WAIT));
+      off += __popcll(em);
     }
+    if (EXTK) n_ex = off;
   }
   if (!same_vms) has_ex = n_ex > 0;
   wsync();
@@ -904,6 +953,9 @@ __device__ __forceinline__ void env_body(const EnvParams &p, const StepOut &o) {
   // external-action kernel neither uses nor keeps them
   int qkind = EXT ? 0 : (((L.hdr->pad >> 62) & 1u) ? 1 : (((L.hdr->pad >> 60) & 1u) ? 2 : 0));
   bool has_ex = (L.hdr->pad >> 61) & 1u;  // bit 61: some VM exists (read with bit 62 only)
+  // the waiting VMs, counted once by the first step's action phase and carried
+  // through the launch by env_tail; the NULL slots the last step left
+  int n_w = 0, null_left = 0;
 #pragma unroll 1
   for (int k = 0; k < k_steps; k++) {
     const bool last = k == k_steps - 1;
@@ -919,11 +971,12 @@ __device__ __forceinline__ void env_body(const EnvParams &p, const StepOut &o) {
     const bool quiet = qkind == 1 || (qkind == 2 && !act_row && !valid_row);
     if (!EXT)
       n_place = heuristic_apply<VPT>(p, L, T, wa, o.policy, act_row, valid_row, quiet, qkind,
-                                     fit_any STAMP_ARGS);
+                                     fit_any, k == 0, n_w STAMP_ARGS);
     else {
       // the external kernel loads the time words after its action phase: live
       // across it beside the 16 action words they spilled 10 VGPRs
-      external_apply<VPT>(p, L, T, wa, o.actions + (int64_t)e * V, valid_row, n_place, n_susp);
+      external_apply<VPT>(p, L, T, wa, o.actions + (int64_t)e * V, valid_row, n_place, n_susp,
+                          n_w);
       if (ONE) {
         const int ln = fresh_lane();
 #pragma unroll
@@ -964,8 +1017,9 @@ __device__ __forceinline__ void env_body(const EnvParams &p, const StepOut &o) {
     }
     wsync();
     bool calm = false;
-    const double r = env_tail<VPT, ONE, SRC>(p, L, T, wa, rem, run0, fb, dirty, vmo, k, EXT, quiet,
-                                        term, calm, has_ex, e STAMP_ARGS);
+    const double r = env_tail<VPT, ONE, SRC, EXT>(p, L, T, wa, rem, run0, fb, dirty, vmo, k, quiet,
+                                        n_place, n_susp, n_w, null_left, term, calm, has_ex,
+                                        e STAMP_ARGS);
     // the next step's skip: nothing fit (1), or every placement was rejected
     // (2); a skipped step passes its kind on while nothing changes
     qkind = (EXT || !calm) ? 0 : quiet ? qkind : (!fit_any ? 1 : (n_place == 0 ? 2 : 0));
@@ -980,7 +1034,7 @@ __device__ __forceinline__ void env_body(const EnvParams &p, const StepOut &o) {
     for (int s = 0; s < VPT; s++) wt[s] = wa[s];
     bool fit_any;
     heuristic_apply<VPT>(p, L, T, wt, o.policy, o.act_out + (int64_t)e * V, nullptr, qkind == 1,
-                         qkind, fit_any STAMP_ARGS);
+                         qkind, fit_any, false, n_w STAMP_ARGS);
   }
   STAMP(0);
   if (o.obs) write_obs<VPT>(p, L, T, wa, o.obs + (int64_t)e * p.D);
@@ -991,6 +1045,9 @@ __device__ __forceinline__ void env_body(const EnvParams &p, const StepOut &o) {
     if (o.done_count && lane == 0) gptr(o.done_count)[e] += ndone;
     const uint32_t t32 = (uint32_t)(L.hdr->timestep - 1);  // this launch's step
     const int ln = fresh_lane();
+    // (per-step launch: most steps change no VM word but the accepted ones,
+    // stored already; one ballot then skips the 16 predicated store blocks)
+    if (!ONE || ballot(dirty != 0u) != 0) {
 #pragma unroll
     for (int s = 0; s < VPT; s++) {
       if (live(wa[s]) && ((dirty >> s) & 1u)) {  // unchanged words stay as they are
@@ -1009,6 +1066,7 @@ __device__ __forceinline__ void env_body(const EnvParams &p, const StepOut &o) {
         }
       }
     }
+    }
     // only the PM words written this launch (place / suspend / free: the
     // precision clamp changes no other value, as every stored value is 0 or
     // >= 1e-7 after the previous launch's clamp)
@@ -1018,11 +1076,14 @@ __device__ __forceinline__ void env_body(const EnvParams &p, const StepOut &o) {
     {  // the next launch's draw hint (predraw): per-step launches only
       uint64_t hint = 0;
       if (ONE) {  // (the NULL count is recorded as 0 or 1: only "none" is read)
-        bool anynull = false;
-#pragma unroll
-        for (int s = 0; s < VPT; s++) anynull |= w_pl(wa[s]) == P + 1;
         uint32_t m = nf;
-        const bool nn = ballot(anynull) != 0;
+        bool nn = null_left > 0;  // env_tail's count: exact (see there)
+        if (EXT) {  // (the external kernels keep the sweep, as for n_ex in env_tail)
+          bool anynull = false;
+#pragma unroll
+          for (int s = 0; s < VPT; s++) anynull |= w_pl(wa[s]) == P + 1;
+          nn = ballot(anynull) != 0;
+        }
         if (!nn && want_nf) {
 #pragma unroll
           for (int o = 32; o > 0; o >>= 1) m = min(m, (uint32_t)__shfl_xor((int)m, o));
