@@ -353,6 +353,63 @@ int vmp_restore(vmp_handle *h, const void *src);
  * vmp_reset with their mask; the observers of kept envs continue. (ABI 14, additive) */
 int vmp_branch(vmp_handle *dst, vmp_handle *src, const int32_t *src_of_dst, const int64_t *seeds);
 
+/* Set env states from the caller's arrays on the device: the inverse of vmp_get_state /
+ * vmp_get_counters. All pointers are DEVICE pointers, in those calls' shapes and dtypes:
+ *  env_mask   u8[n_env], nullable = every env; a zero byte keeps the env
+ *  placement, remaining  int64[n_env][V]; vm_cpu, vm_mem f64[n_env][V]       (required)
+ *  cpu, mem   f64[n_env][P], both given or both NULL
+ *  counters   int64[n_env][VMP_NCTR] (VMP_CTR_*, the timestep included), nullable = kept
+ *  totals     f64[n_env][2]: VMP_ST_TOTAL_CPU_REQ, VMP_ST_TOTAL_MEM_REQ, nullable = kept
+ *  seeds      int64[n_env], nullable; seeds[e] >= 0 gives env e the four streams and sequence
+ *             bases of reset(seed = seeds[e]), seeds[e] < 0 keeps its streams
+ *  status     u8[n_env], nullable: a VMP_SS_* code per env
+ * A selected env is validated as a whole on the device. If every rule holds, all of it is
+ * written (status VMP_SS_IMPORTED); otherwise NOTHING of it is written and status names the
+ * lowest-numbered failing rule. P = pms: placement P is WAIT, P + 1 is NULL (an empty slot).
+ *  VMP_SS_PLACEMENT   a placement outside [0, P + 1]
+ *  VMP_SS_NULL_SLOT   a NULL slot whose sizes or remaining are not 0
+ *  VMP_SS_VM_SIZE     an existing VM whose size is not bitwise (double)k / 100.0, k in 1..100
+ *  VMP_SS_RUNTIME     an existing VM whose remaining is outside [1, 2^30]
+ *  VMP_SS_TIMESTEP    the timestep (counters' if given, else the env's own) outside [1, 2^31)
+ *  VMP_SS_COUNTER     one of the other five counters negative
+ *  VMP_SS_CAPACITY    a PM whose running VMs sum to more than 100 hundredths of cpu or memory
+ *  VMP_SS_LOAD_FLOOR  a given load x that is neither 0 nor >= 1e-7 (NaN included)
+ *  VMP_SS_LOAD_MAX    a given load above 1.0
+ *  VMP_SS_LOAD_SUM    a given load with |x - sum k / 100| >= 1e-7 (env.py:267's threshold)
+ * Written: the VM words of slots 0..V-1 (a running VM's time word is its finish key timestep +
+ * remaining; the words behind slot V stay); the PM row: the given loads verbatim (they carry a
+ * run's rounding history), else (double)(sum of k) / 100.0 per PM, which does not depend on any
+ * order; the six counters and the two totals where given; waiting_ratio = #waiting / #existing
+ * (0 without a VM, env.py:112-115); the step hint word as 0 (the next step takes the general
+ * path); the streams where seeds say so. The target means are derived by vmp_get_stats and by
+ * the steps that need them. Not touched: eval mode, the per-env workload, the trace and its map
+ * (a traced env continues on its own trace at the imported timestep), the launch-order flags.
+ * VMP_EINVAL, the handle unchanged: a null handle, a missing required array, exactly one of
+ * cpu / mem, or more PMs than the kernel's per-PM sums hold in LDS (8190).
+ * Stream-ordered on the handle's stream; allocates nothing and never synchronises, so it may be
+ * captured in a graph and replayed with rewritten arrays. The one exception, as in vmp_branch:
+ * with the recorder, the request log or the time series on, the first call allocates an
+ * n_env-byte mask, so make one call before capturing. Those observers restart for exactly the
+ * imported envs; refused and unselected envs keep theirs. (ABI 14, additive) */
+#define VMP_SS_SKIPPED 0
+#define VMP_SS_IMPORTED 1
+#define VMP_SS_PLACEMENT 2
+#define VMP_SS_NULL_SLOT 3
+#define VMP_SS_VM_SIZE 4
+#define VMP_SS_RUNTIME 5
+#define VMP_SS_TIMESTEP 6
+#define VMP_SS_COUNTER 7
+#define VMP_SS_CAPACITY 8
+#define VMP_SS_LOAD_FLOOR 9
+#define VMP_SS_LOAD_MAX 10
+#define VMP_SS_LOAD_SUM 11
+int vmp_set_state(vmp_handle *h, const uint8_t *env_mask,
+                  const int64_t *placement, const double *vm_cpu, const double *vm_mem,
+                  const int64_t *remaining,
+                  const double *cpu, const double *mem,
+                  const int64_t *counters, const double *totals,
+                  const int64_t *seeds, uint8_t *status);
+
 /* PPOAgent.update GAE (ppo.py:232-243) over T steps x N envs, reverse scan:
  *  delta = r + (1-d)*gamma*v' - v;  g = delta + (1-d)*gamma*lambda*g.
  * All device f32 [T][N] (done as f32 0/1); adv and ret are outputs. */

@@ -19,6 +19,7 @@
 #include "vmp_record.h"
 #include "vmp_reqlog.h"
 #include "vmp_series.h"
+#include "vmp_state.h"
 #include "vmp_trace.h"
 
 using namespace vmp;
@@ -83,7 +84,8 @@ struct vmp_handle {
   uint32_t lo_count;
   int32_t lo_mode, lo_div;
   // vmp_branch: the staging copy of hdr | pm | vmw for dst == src, and the mask of
-  // the overwritten envs that restarts the observers; each allocated on first use
+  // the overwritten envs that restarts the observers (vmp_set_state's too); each
+  // allocated on first use
   uint8_t *br_stage;
   uint8_t *br_mask;
 };
@@ -1183,6 +1185,50 @@ int vmp_branch(vmp_handle *dst, vmp_handle *src, const int32_t *src_of_dst, cons
   if (dst->rq_on)
     if (const int rc = reqlog_init(dst, dst->br_mask)) return rc;
   return dst->sr_on ? series_init(dst, dst->br_mask) : VMP_OK;
+}
+
+// ---- set state: env states from the caller's arrays ----
+// One launch (vmp_state.hip), a workgroup per env: validation and stores happen
+// on the device; the host only refuses calls that cannot be launched
+// (vmp_state.h). The observers of the imported envs restart through the mask
+// the kernel writes, which vmp_branch shares.
+int vmp_set_state(vmp_handle *h, const uint8_t *env_mask, const int64_t *placement,
+                  const double *vm_cpu, const double *vm_mem, const int64_t *remaining,
+                  const double *cpu, const double *mem, const int64_t *counters,
+                  const double *totals, const int64_t *seeds, uint8_t *status) {
+  StateCall c;
+  std::memset(&c, 0, sizeof(c));
+  c.handle = h;
+  c.placement = placement, c.vm_cpu = vm_cpu, c.vm_mem = vm_mem, c.remaining = remaining;
+  c.cpu = cpu, c.mem = mem;
+  c.P = h ? h->P : 1;
+  const char *why = nullptr;
+  if (const int rc = state_check(&c, &why)) return fail(rc, why);
+  const bool observed = h->rec_on || h->rq_on || h->sr_on;
+  if (observed && !h->br_mask) {
+    const hipError_t e = dev_malloc(&h->br_mask, (size_t)h->N);
+    if (e != hipSuccess)
+      return fail(e == hipErrorOutOfMemory ? VMP_EOOM : VMP_EDEVICE,
+                  std::string("vmp_set_state mask: ") + hipGetErrorString(e));
+  }
+  StateArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.hdr = h->hdr, a.pm = h->pm, a.vmw = h->vmw;
+  a.env_mask = env_mask;
+  a.placement = placement, a.vm_cpu = vm_cpu, a.vm_mem = vm_mem, a.remaining = remaining;
+  a.cpu = cpu, a.mem = mem;
+  a.counters = counters, a.totals = totals, a.seeds = seeds;
+  a.status = status;
+  a.imported = observed ? h->br_mask : nullptr;
+  a.N = h->N, a.P = h->P, a.V = h->V;
+  hipLaunchKernelGGL(k_set_state, dim3((unsigned)h->N), dim3(kStateThreads),
+                     (size_t)state_lds_bytes(h->P), h->stream, a);
+  if (const int rc = launched()) return rc;
+  if (h->rec_on)  // the observers of the imported envs restart from the new state
+    if (const int rc = record_init(h, h->br_mask)) return rc;
+  if (h->rq_on)
+    if (const int rc = reqlog_init(h, h->br_mask)) return rc;
+  return h->sr_on ? series_init(h, h->br_mask) : VMP_OK;
 }
 
 int64_t vmp_debug_live_allocs(void) { return g_live.load(); }

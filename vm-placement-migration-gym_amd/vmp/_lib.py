@@ -25,7 +25,7 @@ EXPORTS = (
     "vmp_actor_mlp_f32", "vmp_actor_mlp_head_f32", "vmp_step_mask", "vmp_record_enable",
     "vmp_record_read", "vmp_reqlog_enable", "vmp_reqlog_info", "vmp_reqlog_read",
     "vmp_series_enable", "vmp_series_info", "vmp_series_read",
-    "vmp_snapshot_bytes", "vmp_snapshot", "vmp_restore", "vmp_branch",
+    "vmp_snapshot_bytes", "vmp_snapshot", "vmp_restore", "vmp_branch", "vmp_set_state",
     "vmp_debug_fail_alloc", "vmp_debug_live_allocs", "vmp_debug_stamps", "vmp_debug_occupancy",
     "vmp_debug_quiet_violations", "vmp_debug_launch_order", "vmp_debug_launch_map",
 )
@@ -135,6 +135,7 @@ def lib():
         "vmp_snapshot": (ctypes.c_int, [P, P]),
         "vmp_restore": (ctypes.c_int, [P, P]),
         "vmp_branch": (ctypes.c_int, [P, P, P, P]),
+        "vmp_set_state": (ctypes.c_int, [P] * 12),
         "vmp_debug_fail_alloc": (ctypes.c_int, [i32]),
         "vmp_debug_live_allocs": (ctypes.c_int64, []),
         "vmp_debug_stamps": (ctypes.c_int, [P, P]),

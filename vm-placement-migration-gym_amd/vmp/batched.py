@@ -54,6 +54,7 @@ class BatchedVmEnv:
                                    ctypes.byref(h)))
         self._h = h
         self._traces = None
+        self._start = None  # set_start_state: what reset() leaves instead of an empty env
         if arrival_rate is not None or service_length is not None:
             try:
                 self.set_workload(arrival_rate, service_length)
@@ -194,6 +195,11 @@ class BatchedVmEnv:
             m = torch.as_tensor(mask, device=self.device).to(torch.uint8).contiguous()
         o = self._empty((self.n_envs, self.D), torch.float32) if obs else None
         check(lib().vmp_reset(h, ptr(s), ptr(m), ptr(o)))
+        if self._start is not None:  # validated on the host by set_start_state: no read-back here
+            st, ctr, tot = self._start
+            self.set_state(st, mask=m, counters=ctr, totals=tot, check=False)
+            if o is not None:
+                check(lib().vmp_get_obs(h, ptr(o)))
         return o
 
     def step(self, actions, obs=None, reward=None, done=None, valid=None, want_valid=True,
@@ -505,3 +511,93 @@ class BatchedVmEnv:
         m = self._branch_arg(index, torch.int32, "index", -1, src.n_envs)
         s = None if seeds is None else self._branch_arg(seeds, torch.int64, "seeds")
         check(lib().vmp_branch(hd, hs, ptr(m), ptr(s)))
+
+    # ------------------------------------------------------------ set state
+    def _state_arg(self, x, dtype, shape, name):
+        """An array of `set_state` as a contiguous device tensor of `shape`. A
+        device tensor of the right dtype and layout is used as it is (a graph
+        replays on the caller's own buffer); anything else is converted."""
+        if isinstance(x, torch.Tensor):
+            if x.is_cuda and x.device != self.device:
+                raise ValueError(f"{name} lives on {x.device}, the env on {self.device}")
+            t = x
+        else:
+            a = np.asarray(x)
+            if a.dtype.kind not in "iufb":
+                raise ValueError(f"{name} must be numeric")
+            t = torch.from_numpy(np.ascontiguousarray(a))
+        if tuple(t.shape) != tuple(shape):
+            raise ValueError(f"{name} must have shape {tuple(shape)}, not {tuple(t.shape)}")
+        return t.to(device=self.device, dtype=dtype).contiguous()
+
+    def set_start_state(self, state):
+        """Make every later reset() leave `state` (a vmp.state.State of n_envs
+        envs, or of one env for all; None: an empty env again) instead of an
+        empty env: the reset envs are reseeded or rewound as usual and then
+        given the state by set_state, counters and totals included where the
+        state has them. The state is validated here, on the host (ValueError),
+        and kept on the device, so reset() stays free of host synchronisation."""
+        if state is None:
+            self._start = None
+            return
+        from .state import IMPORTED, RULES
+        s = state.broadcast(self.n_envs)
+        if s.pms != self.P or s.vms != self.V:
+            raise ValueError(f"the state is of {s.pms} PMs / {s.vms} VMs, the env of "
+                             f"{self.P} / {self.V}")
+        code = s.validate(timestep=1)
+        if (code != IMPORTED).any():
+            e = int(np.flatnonzero(code != IMPORTED)[0])
+            raise ValueError(f"start state refused, env {e}: {RULES[int(code[e])]}")
+        dev = lambda x: None if x is None else torch.as_tensor(x, device=self.device)  # noqa: E731
+        self._start = ({k: dev(v) for k, v in s.as_dict().items()}, dev(s.counters), dev(s.totals))
+
+    def set_state(self, state, mask=None, counters=None, totals=None, seeds=None, check=True):
+        """Give envs the state in the caller's arrays (vmp_set_state): the
+        inverse of `state()` / `counters()`. state: the dict `state()` returns
+        (vm_placement, vm_remaining_runtime int64 [N, V]; vm_cpu, vm_memory f64
+        [N, V]); cpu / memory f64 [N, P] may be absent or None, the PM loads are
+        then the exact sums of the running VMs' hundredths. mask [N]: the envs
+        to set (None: all). counters int64 [N, 6] as `counters()` returns them
+        (timestep last), totals f64 [N, 2] = total cpu / memory requested; None
+        keeps the env's. seeds int64 [N]: entries >= 0 give the env the streams
+        of reset(seed), negative ones and None keep its streams.
+        Every selected env is validated on the device as a whole and written
+        only if valid (vmp.state.RULES names the codes). check=True reads the
+        status back and raises ValueError naming the refused envs and their
+        rule; check=False returns the status tensor (u8 [N]: 0 not selected, 1
+        imported, >= 2 refused) without a synchronise: with device tensors of
+        the right dtype this is the graph-capturable form, and a replay reads
+        the tensors' current contents. Host lists and arrays are converted;
+        a shape mismatch raises ValueError. The recorder, request log and
+        series restart for the imported envs only."""
+        h = self._bind()
+        N, V, P = self.n_envs, self.V, self.P
+        pl = self._state_arg(state["vm_placement"], torch.int64, (N, V), "vm_placement")
+        vc = self._state_arg(state["vm_cpu"], torch.float64, (N, V), "vm_cpu")
+        vm = self._state_arg(state["vm_memory"], torch.float64, (N, V), "vm_memory")
+        rem = self._state_arg(state["vm_remaining_runtime"], torch.int64, (N, V),
+                              "vm_remaining_runtime")
+        c, m = state.get("cpu"), state.get("memory")
+        if (c is None) != (m is None):
+            raise ValueError("cpu and memory are both given or both absent")
+        if c is not None:
+            c = self._state_arg(c, torch.float64, (N, P), "cpu")
+            m = self._state_arg(m, torch.float64, (N, P), "memory")
+        k = None if mask is None else self._state_arg(mask, torch.uint8, (N,), "mask")
+        ctr = None if counters is None else self._state_arg(counters, torch.int64,
+                                                            (N, N_COUNTERS), "counters")
+        tot = None if totals is None else self._state_arg(totals, torch.float64, (N, 2), "totals")
+        sd = None if seeds is None else self._state_arg(seeds, torch.int64, (N,), "seeds")
+        status = self._empty((N,), torch.uint8)
+        _lib.check(lib().vmp_set_state(h, ptr(k), ptr(pl), ptr(vc), ptr(vm), ptr(rem), ptr(c),
+                                       ptr(m), ptr(ctr), ptr(tot), ptr(sd), ptr(status)))
+        if not check:
+            return status
+        st = status.cpu().numpy()
+        refused = np.flatnonzero(st >= 2)
+        if refused.size:
+            from .state import RULES
+            raise ValueError("set_state refused env(s) " + ", ".join(
+                f"{int(e)}: {RULES.get(int(st[e]), int(st[e]))}" for e in refused))
+        return status

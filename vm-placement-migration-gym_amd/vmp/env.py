@@ -84,6 +84,33 @@ class VmEnv(_GymEnv):
         requests observed."""
         return self._b.request_log_read().env(0)
 
+    def set_start_state(self, state):
+        """Every later reset() starts from `state` (a one-env vmp.state.State;
+        None: from an empty env again), BatchedVmEnv.set_start_state."""
+        self._b.set_start_state(state)
+
+    def set_state(self, state, counters=None, totals=None, seed=None, check=True):
+        """Continue from the caller's state (BatchedVmEnv.set_state for one
+        env). state: a dict of numpy arrays under the reference's attribute
+        names (vm_placement, vm_cpu, vm_memory, vm_remaining_runtime [vms];
+        cpu, memory [pms] optional), or a one-env vmp.state.State, whose
+        counters and totals are used where none are passed. counters [6] as
+        the reference counts them (timestep last), totals [2]; None keeps the
+        env's own. seed >= 0 reseeds the four streams as reset(seed) does.
+        Raises ValueError for a state the env refuses. Returns the observation."""
+        from .state import State
+        if isinstance(state, State):
+            counters = state.counters if counters is None else counters
+            totals = state.totals if totals is None else totals
+            state = state.as_dict()
+        one = {k: np.asarray(v)[None] if np.asarray(v).ndim == 1 else np.asarray(v)
+               for k, v in state.items() if v is not None}
+        row = lambda x: None if x is None else np.asarray(x).reshape(1, -1)
+        self._b.set_state(one, counters=row(counters), totals=row(totals),
+                          seeds=None if seed is None else [int(seed)], check=check)
+        self.vm_arrival_steps = [[] for _ in range(self.config.vms)]
+        return self._b.obs()[0].cpu().numpy()
+
     # ------------------------------------------------------- state views
     def _st(self):
         return {k: v[0].cpu().numpy() for k, v in self._b.state().items()}

@@ -15,6 +15,7 @@ comes back to the host. This replaces the reference's process fan-out
     python -m vmp.exp migration_ratio --agents bestfit,ppo --weights 'w/ppo-{reward}.pt'
     python -m vmp.exp paired --trace a.npz,b.npz           # every agent on the same requests
     python -m vmp.exp paired --trace a.npz --requests r.csv   # ... and what became of each request
+    python -m vmp.exp paired --trace a.npz --state s.npz      # ... from a saved cluster state
     python -m vmp.exp suspension --series s.csv --series-stride 100   # any experiment: curves over time
 
 Rows are printed in exp_suspension.py's CSV layout (exp_suspension.py:51-58):
@@ -286,19 +287,24 @@ def paired_row(agent, index, trace, summary):
 
 
 def paired_sweep(traces, agents=("firstfit", "bestfit"), config=None, eval_steps=None,
-                 weights=None, device="cuda:0", series=None):
+                 weights=None, device="cuda:0", series=None, state=None):
     """Every agent on the SAME requests: one handle per agent whose env i replays
     traces[i] (BatchedVmEnv.set_trace), the device recorder on, eval_steps steps
     (default: the longest trace). A traced env's requests do not depend on what
     the policy did with the earlier ones, so the rows of one trace compare the
     agents on one workload. One CSV row per (agent, trace), see PAIRED_HEADER.
     series=(stride, path): also write the time series CSV, one row per agent
-    and window over the agent's envs (run_cells)."""
-    return _paired_run(traces, agents, config, eval_steps, weights, device, False, series)[0]
+    and window over the agent's envs (run_cells). state: a vmp.state.State the
+    envs start from instead of an empty env (BatchedVmEnv.set_start_state); a
+    state with counters brings its timestep, which selects the trace step."""
+    return _paired_run(traces, agents, config, eval_steps, weights, device, False, series,
+                       state)[0]
 
 
-def _paired_run(traces, agents, config, eval_steps, weights, device, log, series=None):
-    """paired_sweep's runs; log=True: with the per-request outcome log on.
+def _paired_run(traces, agents, config, eval_steps, weights, device, log, series=None,
+                state=None):
+    """paired_sweep's runs; log=True: with the per-request outcome log on;
+    state: a vmp.state.State every env starts from (one env row serves all).
     Returns (rows, {agent: RequestLog})."""
     series = _series_request(series)
     series_out = []
@@ -313,6 +319,7 @@ def _paired_run(traces, agents, config, eval_steps, weights, device, log, series
         env = BatchedVmEnv(Config(**cfg), len(traces), device=device)
         env.set_trace(traces, np.arange(len(traces)))  # before any capture: it switches kernels
         env.eval(True)
+        env.set_start_state(state)
         env.reset()
         env.record(True)
         if log:  # before the capture below: a graph captured earlier would not log
@@ -574,6 +581,9 @@ def arg_parser():
     ap.add_argument("--merge", action="store_true",
                     help="suspension: one handle per heuristic agent, a per-env workload per cell")
     ap.add_argument("--trace", default=None, help="paired: comma list of Trace .npz files")
+    ap.add_argument("--state", default=None,
+                    help="paired: a vmp.state.State .npz every env starts from (one env row "
+                         "serves all envs), not an empty env")
     ap.add_argument("--config", default=None,
                     help="paired: YAML with an `environment:` section (default config/100.yml's, wr)")
     ap.add_argument("--requests", default=None,
@@ -609,8 +619,12 @@ def main(argv=None):
                 cfg["reward_function"] = a.reward
         header = PAIRED_HEADER
         traces = [Trace.load(p) for p in a.trace.split(",")]
+        state = None
+        if a.state:
+            from .state import State
+            state = State.load(a.state)
         rows, logs = _paired_run(traces, agents, cfg, a.eval_steps, a.weights, "cuda:0",
-                                 a.requests is not None, series)
+                                 a.requests is not None, series, state)
         if a.requests is not None:
             with open(a.requests, "w") as f:
                 f.write("\n".join([paired_requests_header(agents)]

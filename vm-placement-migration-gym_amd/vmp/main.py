@@ -9,7 +9,9 @@ load-or-learn-then-save weights logic (main.py:65-77) and `agent.test` eval
 exp_* drivers call it). Additions: `--envs N` trains PPO on N batched GPU envs
 (the reference trains one), `--device`, and `--trace FILE.npz`: the env replays
 the requests of a vmp.trace.Trace file instead of drawing them (training and
-eval alike; `--envs N` training replays it on every env). The drlvmp / convex / rainbow agents
+eval alike; `--envs N` training replays it on every env), and `--state FILE.npz`:
+every reset leaves the env state of a vmp.state.State file (one env row serves
+all envs) instead of an empty env. The drlvmp / convex / rainbow agents
 are out of scope and raise.
 """
 import argparse
@@ -39,6 +41,7 @@ class Args:
     envs: int = 1
     device: str = "cuda"
     trace: str = None
+    state: str = None
 
 
 def _known(cls, d):
@@ -79,6 +82,11 @@ def run(args: Args):
         from .trace import Trace
         trace = Trace.load(args.trace)
         env.set_trace(trace)
+    state = None
+    if args.state:
+        from .state import State
+        state = State.load(args.state)
+        env.set_start_state(state)
     agent = make_agent(args.agent, env, agent_config)
     if args.logdir and args.jobname:
         agent.set_log(jobname=args.jobname, logdir=args.logdir)
@@ -90,6 +98,7 @@ def run(args: Args):
             benv = BatchedVmEnv(env.config, args.envs, device=env._b.device)
             if trace is not None:
                 benv.set_trace(trace)
+            benv.set_start_state(state)
             trainer = make_agent("ppo", benv, agent_config)
             trainer.learn()
             agent.model.load_state_dict(trainer.model.state_dict())
@@ -138,13 +147,15 @@ def parse(argv=None):
     p.add_argument("--device", default="cuda")
     p.add_argument("--trace", default=None,
                    help="replay the requests of this Trace .npz instead of drawing them")
+    p.add_argument("--state", default=None,
+                   help="start every episode from this vmp.state.State .npz, not from an empty env")
     a = p.parse_args(argv)
     import yaml
     with open(a.config) as f:
         cfg = yaml.safe_load(f)
     return Args(agent=a.agent, reward=a.reward, config=cfg, logdir=a.logdir, output=a.output,
                 silent=a.silent, jobname=a.jobname, weightspath=a.weightspath, eval=a.eval,
-                debug=a.debug, envs=a.envs, device=a.device, trace=a.trace)
+                debug=a.debug, envs=a.envs, device=a.device, trace=a.trace, state=a.state)
 
 
 if __name__ == "__main__":
