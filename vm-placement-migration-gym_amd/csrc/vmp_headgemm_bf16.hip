@@ -5,8 +5,8 @@
 //
 // Forward (GIVEN actions): logits = h W^T + b are formed tile by tile with
 // v_mfma_f32_16x16x32_bf16 (bf16 h and W, f32 accumulate) and consumed in
-// registers: masked max / sum / lse, entropy lse - (sum p x)/S and the given
-// action's logprob per (sample, VM row) -> row buffers -> k_rowsum. The
+// registers: masked max m / sum / lse, entropy (lse - m) - (sum p (x - m))/S and
+// the given action's logprob per (sample, VM row) -> row buffers -> k_rowsum. The
 // [B, V*A] logits never reach HBM.
 // Backward: the same tiles are recomputed, and dlogits
 //   d_j = -q_j (g_lp + g_ent (x_j - lse + H)) + g_lp [j = a],  0 at masked j
@@ -38,6 +38,7 @@
 
 #include "../../include/vmp.h"
 #include "vmp_head_dev.h"
+#include "vmp_hg16_plan.h"
 
 #define LDSP __attribute__((address_space(3)))
 #define GLBP __attribute__((address_space(1)))
@@ -55,15 +56,14 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 
-constexpr int kBM = 256;       // samples per M block (NW waves x MC 16-sample columns)
+constexpr int kBM = kHg16BM;   // samples per M block (NW waves x MC 16-sample columns)
 constexpr int kBK = 64;        // K per LDS stage
 constexpr int kRow = 2 * kBK;  // bytes per staged row
-constexpr int kMaxNT = 14;     // 16-column accumulator tiles per workgroup
+constexpr int kMaxNT = kHg16MaxNT;  // 16-column accumulator tiles per workgroup
 constexpr float kMasked = -1e7f;   // ppo.py:119
 constexpr float kPad = -1e30f;     // tile columns past A: p = 0, never the max
 constexpr float kLog2e = 1.44269504088896341f;
 constexpr int kPipe = 4;       // W fragments in flight ahead of their MFMAs
-constexpr int kTeam = 8;       // XCD team size (hg16_tile)
 
 struct H16Args {
   int B, K, V, A, W32, n_tiles, m_blocks, m_groups, ld;
@@ -192,7 +192,7 @@ __device__ __forceinline__ void load_mask(const H16Args &a, int64_t row, uint32_
 // of one XCD take the same column tile (its W tile stays in that XCD's L2
 // while they walk M blocks j, j + G, ...) and the 32 / team teams resident on
 // an XCD walk the same M blocks (h tiles shared): at team 8, an L2 working set
-// of 4 W tiles + 8 h tiles instead of 32 W tiles (kTeam; 0 / 2 / 4 / 8
+// of 4 W tiles + 8 h tiles instead of 32 W tiles (kHg16Team; 0 / 2 / 4 / 8
 // measured, profiles/r04_hg16_team.log). False: a padding block.
 __device__ __forceinline__ bool hg16_tile(const H16Args &a, int &n_tile, int &g) {
   if (a.team > 0) {
@@ -362,16 +362,23 @@ struct Hg16Epi {
     }
     mx = xmax(mx);
     // pass 2: p = exp(x - m) (x - m first: exact at x = m, so an all-masked
-    // row gets p = 1 everywhere, as the unfused head), S, T = sum p x
+    // row gets p = 1 everywhere, as the unfused head), S, T = sum p (x - m).
+    // From here on xm holds x - m: logprob, entropy and dlogits are formed
+    // from x - m and L = lse - m, differences that do not round at the size
+    // of x (with sum p x and x - lse the bias gradient, a sum over the batch
+    // of such roundings, missed its f64 value by 5 x torch's f32 error at
+    // |x| ~ 150; tests/test_gpu_hg16_instances.py)
     float p[TS][4];
     float Ss = 0.f, Ts = 0.f;
 #pragma unroll
     for (int u = 0; u < TS; u++)
 #pragma unroll
       for (int r = 0; r < 4; r++) {
-        p[u][r] = __builtin_amdgcn_exp2f((xm[u][r] - mx) * kLog2e);
+        const float t = xm[u][r] - mx;
+        p[u][r] = __builtin_amdgcn_exp2f(t * kLog2e);
         Ss += p[u][r];
-        Ts = __builtin_fmaf(p[u][r], xm[u][r], Ts);
+        Ts = __builtin_fmaf(p[u][r], t, Ts);
+        xm[u][r] = t;
       }
     float xa = 0.f;
     if (!BWD && !SMP) {  // the given action's logit: tile u_t, register r_t of lane q_t
@@ -386,9 +393,14 @@ struct Hg16Epi {
     }
     Ss = xsum(Ss);
     Ts = xsum(Ts);
+    // lse is rounded to f32 once, as torch's logsumexp (an all-masked row:
+    // at 1e7, where L comes out as an integer); L = lse - m is exact when lse
+    // and m are within a factor of two, and otherwise (|m| small against
+    // log S) rounds at the size of L, not of x
     const float lse = mx + logf(Ss);
+    const float L = lse - mx;
     const float inv = 1.0f / Ss;
-    const float H = lse - Ts * inv;  // Categorical.entropy, the tiled head's order
+    const float H = L - Ts * inv;  // Categorical.entropy = lse - sum q x, m taken out of both
     if (!BWD && SMP) {
       // inverse CDF over the row in action order j = 16 u + 4 q + r: the tile
       // totals T[u] (same value on every lane), the tile u* holding target,
@@ -481,17 +493,17 @@ struct Hg16Epi {
       }
       if (live && q == 0) {
         a.act_out[row] = jb;
-        a.row_lp[row] = xb - lse;
+        a.row_lp[row] = xb - L;
         a.row_ent[row] = H;
       }
     } else if (!BWD) {
       xa = xsum(xa);  // one lane-element holds it, the others 0
       if (live && q == 0) {
-        a.row_lp[row] = tgt >= 0 ? xa - lse : NAN;
+        a.row_lp[row] = tgt >= 0 ? xa - L : NAN;
         a.row_ent[row] = H;
       }
     } else {
-      const float c1 = glp + gen * (H - lse);
+      const float c1 = glp + gen * (H - L);  // d = -q (g_lp + g_ent ((x - m) - L + H))
       // pass 1's per-element mask compares are recomputed from the nibbles
       // here (kept live across pass 2 they are 64-bit SGPR pairs each, and
       // spilled)
@@ -664,30 +676,8 @@ constexpr size_t lds_bytes() {
 }
 static_assert(lds_bytes<1>() <= 160 * 1024, "stages exceed LDS");
 
-int pick_ts(int A) { return (A + 15) / 16; }  // segment width: 16 TS columns, TS = ceil(A / 16)
-
-// M groups: the grid is n_tiles x m_groups workgroups at one per CU; pick the
-// group count whose last dispatch round is fullest (ties: fewer workgroups)
-int pick_groups(int n_tiles, int m_blocks) {
-  int best = 1;
-  double best_eff = -1.0;
-  for (int g = 1; g <= m_blocks && g <= 64; g++) {
-    const int64_t wg = (int64_t)n_tiles * g;
-    const double rounds = (double)((wg + 255) / 256);
-    const double eff = (double)wg / (rounds * 256.0);
-    if (eff > best_eff + 1e-9) {
-      best_eff = eff;
-      best = g;
-    }
-    if (eff > 0.97) break;
-  }
-  return best;
-}
-
 template <bool BWD, int NW, bool SMP = false>
-hipError_t launch_ts(const H16Args &a, int TS, hipStream_t st) {
-  const int64_t n_wg = a.team > 0 ? (int64_t)(a.teams + 7) / 8 * 8 * a.team
-                                  : (int64_t)a.n_tiles * a.m_groups;
+hipError_t launch_ts(const H16Args &a, int TS, int64_t n_wg, hipStream_t st) {
   const dim3 grid((unsigned)n_wg), block(64 * NW);
   switch (TS) {
 #define VMP_HG16_CASE(T) \
@@ -702,34 +692,12 @@ hipError_t launch_ts(const H16Args &a, int TS, hipStream_t st) {
 
 template <bool BWD, bool SMP = false>
 hipError_t launch_hg16(H16Args &a, hipStream_t st) {
-  const int TS = pick_ts(a.A);
-  const int S = kMaxNT / TS;
-  a.n_tiles = (a.V + S - 1) / S;
-  a.m_blocks = (a.B + kBM - 1) / kBM;
-  const int team = kTeam;
-  a.team = 0;
-  if (team > 0 && a.m_blocks >= team) {
-    // r walks per team member: the grid n_tiles x team x r (rounded to whole
-    // teams per XCD) whose last round of 256 one-per-CU workgroups is fullest
-    int best = 1;
-    double best_eff = -1.0;
-    for (int r = 1; r * team <= a.m_blocks && r <= 64; r++) {
-      const int64_t teams = (int64_t)a.n_tiles * r;
-      const int64_t wg = (teams + 7) / 8 * 8 * team;
-      const double eff = (double)(teams * team) / ((double)((wg + 255) / 256) * 256.0);
-      if (eff > best_eff + 1e-9) {
-        best_eff = eff;
-        best = r;
-      }
-      if (eff > 0.97) break;
-    }
-    a.team = team;
-    a.teams = a.n_tiles * best;
-    a.m_groups = team * best;
-  } else {
-    a.m_groups = pick_groups(a.n_tiles, a.m_blocks);
-  }
-  return launch_ts<BWD, 8, SMP>(a, TS, st);
+  // segment width, column tiles, M blocks, M groups or XCD teams, grid size:
+  // vmp_hg16_plan.h (swept on the CPU by tests/native/hg16_plan.cpp)
+  const Hg16Plan p = hg16_plan(a.B, a.V, a.A);
+  a.n_tiles = p.n_tiles, a.m_blocks = p.m_blocks;
+  a.team = p.team, a.teams = p.teams, a.m_groups = p.m_groups;
+  return launch_ts<BWD, 8, SMP>(a, p.TS, p.grid, st);
 }
 
 int check_common(int32_t B, int32_t K, int32_t V, int32_t A, const void *h, const void *w,
@@ -883,10 +851,8 @@ extern "C" int vmp_actor_head_bf16_bwd(int32_t B, int32_t K, int32_t V, int32_t 
   return VMP_OK;
 }
 
-// floats of bias-gradient partials vmp_actor_head_bf16_bwd may use: V*A per M
-// group, at most 64 groups x 8 (XCD teams) of 256-sample blocks
+// floats of bias-gradient partials vmp_actor_head_bf16_bwd may use
+// (vmp_hg16_plan.h: V*A per M group)
 extern "C" int64_t vmp_actor_head_bf16_bwd_workspace(int32_t B, int32_t V, int32_t A) {
-  const int64_t blocks = ((int64_t)B + kBM - 1) / kBM;
-  const int64_t groups = blocks < 512 ? blocks : 512;
-  return (groups < 1 ? 1 : groups) * (int64_t)V * A;
+  return hg16_bwd_workspace(B, V, A);
 }
