@@ -65,6 +65,8 @@ def lib():
             "oracle_mask": (None, [P, P]), "oracle_firstfit": (None, [P, P]),
             "oracle_bestfit": (None, [P, P]), "oracle_rank": (i64, [P]),
             "oracle_get_state": (None, [P] * 7), "oracle_get_counters": (None, [P, P, P]),
+            "oracle_assign": (None, [P, P]), "oracle_reseed": (None, [P, i64]),
+            "oracle_set_state": (None, [P] * 9), "oracle_set_workload": (None, [P, dbl, dbl]),
             "oracle_pcg_seed": (None, [u64, P]), "oracle_pcg_raw": (None, [u64, i64, P]),
             "oracle_pcg_double": (None, [u64, i64, P]),
             "oracle_pcg_around": (None, [u64, i64, dbl, dbl, P]),
@@ -155,6 +157,34 @@ class OracleEnv:
         st = np.zeros(5)
         lib().oracle_get_counters(self._h, _p(c), _p(st))
         return c, st
+
+    # the rest of the batched handle's state-changing API, one env at a time
+    def assign(self, other):
+        """vmp_branch: take `other`'s complete state (same P / V), streams and
+        sequence bases included; eval mode and workload stay this env's own."""
+        assert (self.P, self.V) == (other.P, other.V)
+        lib().oracle_assign(self._h, other._h)
+
+    def reseed(self, seed):
+        """The four streams of reset(seed), nothing else (branch / set_state seeds=)."""
+        lib().oracle_reseed(self._h, int(seed))
+
+    def set_state(self, placement, vm_cpu, vm_mem, remaining, cpu=None, mem=None, counters=None,
+                  totals=None):
+        """vmp_set_state of a valid state; not validated (tests/state_literal.validate)."""
+        i8 = lambda a, n: np.ascontiguousarray(a, dtype=np.int64).reshape(n)  # noqa: E731
+        f8 = lambda a, n: np.ascontiguousarray(a, dtype=np.float64).reshape(n)  # noqa: E731
+        assert (cpu is None) == (mem is None)
+        keep = [i8(placement, self.V), f8(vm_cpu, self.V), f8(vm_mem, self.V), i8(remaining, self.V),
+                None if cpu is None else f8(cpu, self.P), None if mem is None else f8(mem, self.P),
+                None if counters is None else i8(counters, 6),
+                None if totals is None else f8(totals, 2)]
+        lib().oracle_set_state(self._h, *[None if a is None else _p(a) for a in keep])
+
+    def set_workload(self, arrival_rate, service_length):
+        """vmp_set_workload: the rates from the next step on."""
+        self.cfg.update(arrival_rate=float(arrival_rate), service_length=float(service_length))
+        lib().oracle_set_workload(self._h, float(arrival_rate), float(service_length))
 
 
 def rollout(cfg: dict, n_env, seed0, stride, steps, policy=0, eval_mode=True, threads=1):

@@ -7,6 +7,8 @@
  *     negative and out-of-range actions, env.py:35-42) for wr / ut / kl and
  *     the three size sequences, incl. drops (V small against the load) and
  *     reset(seed=None) continuations (env.py:180-226);
+ *   - assign / set_state / reseed / set_workload (the models of vmp_branch,
+ *     vmp_set_state and vmp_set_workload) in the middle of those runs;
  *   - the OpenMP batched rollouts (the CPU baseline of bench.py);
  *   - the scalar-introsort argsort on tie-heavy and NaN keys (bestfit.py:33)
  *     and the numpy RNG known-answer entry points.
@@ -32,6 +34,12 @@ int64_t oracle_rank(const oenv *e);
 void oracle_get_state(const oenv *e, int64_t *placement, double *vm_cpu, double *vm_mem,
                       double *cpu, double *mem, int64_t *remaining);
 void oracle_get_counters(const oenv *e, int64_t *c, double *st);
+void oracle_assign(oenv *dst, const oenv *src);
+void oracle_reseed(oenv *e, int64_t seed);
+void oracle_set_state(oenv *e, const int64_t *placement, const double *vm_cpu, const double *vm_mem,
+                      const int64_t *remaining, const double *cpu, const double *mem,
+                      const int64_t *counters, const double *totals);
+void oracle_set_workload(oenv *e, double arrival_rate, double service_length);
 void oracle_pcg_seed(uint64_t seed, uint64_t out[4]);
 void oracle_pcg_raw(uint64_t seed, int64_t n, uint64_t *out);
 void oracle_pcg_double(uint64_t seed, int64_t n, double *out);
@@ -83,6 +91,24 @@ static void run_env(vmp_config c, int steps, int mode) {
     (void)oracle_rank(e);
     oracle_get_counters(e, ctr, st);
     if (t == steps / 2) oracle_reset(e, 0, 0);  /* reset(seed=None): streams continue */
+    /* the handle's other writers: a copy into a second env, an identity import
+     * (loads verbatim, then as sums; with and without counters and totals), a
+     * reseed and a change of workload, each followed by more steps */
+    if (t % 50 == 20) {
+      oenv *twin = oracle_create(&c);
+      oracle_assign(twin, e);
+      oracle_firstfit(twin, act);
+      oracle_step(twin, act, valid, &r, &term);
+      oracle_destroy(twin);
+    }
+    if (t % 50 == 30) {
+      const double tot[2] = {st[3], st[4]};
+      oracle_get_state(e, pl, vc, vm, cpu, mem, rem);
+      oracle_set_state(e, pl, vc, vm, rem, cpu, mem, ctr, tot);
+      oracle_set_state(e, pl, vc, vm, rem, NULL, NULL, NULL, NULL);
+    }
+    if (t % 50 == 40) oracle_reseed(e, c.seed + t);
+    if (t % 100 == 45) oracle_set_workload(e, t % 200 == 45 ? 11.0 : c.arrival_rate, 3.0 + t % 7);
   }
   oracle_reset(e, 1, c.seed + 12);
   oracle_destroy(e);

@@ -514,8 +514,9 @@ static double kl_reward(double tcm, double tmm, double tcv, double tmv, double c
   return -kl;
 }
 
-/* _process_action stats + reward (env.py:112-156). */
-static double stats_reward(oenv *e) {
+/* env.py:112-121 on the state as it stands: waiting ratio and capped target
+ * means; the existing VMs' sizes are left in tmp / tmp2. Returns their count. */
+static int64_t state_stats(oenv *e) {
   int64_t n_ex = 0, n_w = 0;
   for (int v = 0; v < e->V; v++) {
     if (e->placement[v] <= e->WAIT) {
@@ -530,6 +531,12 @@ static double stats_reward(oenv *e) {
   if (e->cfg.cap_target_util && e->tcm > 1) e->tcm = 1.0;
   e->tmm = np_sum(e->tmp2, n_ex) / (double)e->P;
   if (e->cfg.cap_target_util && e->tmm > 1) e->tmm = 1.0;
+  return n_ex;
+}
+
+/* _process_action stats + reward (env.py:112-156). */
+static double stats_reward(oenv *e) {
+  const int64_t n_ex = state_stats(e);
   if (n_ex == 0) return 0.0;
   switch (e->cfg.reward_function) {
     case VMP_REWARD_KL: {
@@ -699,6 +706,78 @@ void oracle_get_counters(const oenv *e, int64_t *c, double *st) {
   st[2] = e->tmm;
   st[3] = e->total_cpu_req;
   st[4] = e->total_mem_req;
+}
+
+/* ------------------------------------- the rest of the handle's state API -- */
+/* The models of vmp_branch, vmp_set_state(seeds) and vmp_set_workload for the
+ * call-sequence tests (tests/seq_cases.py). */
+static void oenv_assign(oenv *d, const oenv *s);
+
+/* vmp_branch for one env: dst takes src's complete state (VM and PM arrays,
+ * counters, totals, stats, the four streams and the two sequence bases; the
+ * configs have the same P / V). Eval mode and the workload stay dst's own. */
+void oracle_assign(oenv *dst, const oenv *src) {
+  const int mode = dst->eval_mode;
+  oenv_assign(dst, src);
+  dst->eval_mode = mode;
+}
+
+/* The four streams and two sequence bases of reset(seed), nothing else: what
+ * branch(seeds=) and set_state(seeds=) give an env. */
+void oracle_reseed(oenv *e, int64_t seed) {
+  for (int k = 0; k < 4; k++) pcg_seed(&e->rng[k], (uint64_t)(seed + k));
+  e->seq_base[0] = e->rng[0];
+  e->seq_base[1] = e->rng[1];
+}
+
+/* vmp_set_state of a VALID state (no validation here: tests/state_literal.py
+ * gives the verdict). cpu / mem NULL: every PM's load is the sum of its running
+ * VMs' hundredths over 100.0. counters [6] (timestep last) / totals [2] NULL:
+ * the env keeps its own. The streams are not touched. */
+void oracle_set_state(oenv *e, const int64_t *placement, const double *vm_cpu, const double *vm_mem,
+                      const int64_t *remaining, const double *cpu, const double *mem,
+                      const int64_t *counters, const double *totals) {
+  int V = e->V, P = e->P;
+  memcpy(e->placement, placement, sizeof(int64_t) * V);
+  memcpy(e->remaining, remaining, sizeof(int64_t) * V);
+  memcpy(e->vm_cpu, vm_cpu, sizeof(double) * V);
+  memcpy(e->vm_mem, vm_mem, sizeof(double) * V);
+  if (cpu && mem) {
+    memcpy(e->cpu, cpu, sizeof(double) * P);
+    memcpy(e->mem, mem, sizeof(double) * P);
+  } else {
+    int64_t *sc = (int64_t *)calloc(2 * (size_t)P, sizeof(int64_t));
+    for (int v = 0; v < V; v++) {
+      int64_t q = placement[v];
+      if (q < 0 || q >= P) continue;
+      sc[q] += (int64_t)rint(vm_cpu[v] * 100.0);
+      sc[P + q] += (int64_t)rint(vm_mem[v] * 100.0);
+    }
+    for (int p = 0; p < P; p++) {
+      e->cpu[p] = (double)sc[p] / 100.0;
+      e->mem[p] = (double)sc[P + p] / 100.0;
+    }
+    free(sc);
+  }
+  if (counters) {
+    e->total_requests = counters[0];
+    e->served = counters[1];
+    e->suspend_action = counters[2];
+    e->place_action = counters[3];
+    e->dropped = counters[4];
+    e->timestep = counters[5];
+  }
+  if (totals) {
+    e->total_cpu_req = totals[0];
+    e->total_mem_req = totals[1];
+  }
+  state_stats(e);
+}
+
+/* vmp_set_workload for one env: the rates its next step draws with. */
+void oracle_set_workload(oenv *e, double arrival_rate, double service_length) {
+  e->cfg.arrival_rate = arrival_rate;
+  e->cfg.service_length = service_length;
 }
 
 /* -------------------------------------------------------- RNG test hooks -- */

@@ -16,7 +16,7 @@ import numpy as np
 import pytest
 import torch
 
-from oracle import oracle as O
+from tests.act_literal import literal_act
 
 pytestmark = pytest.mark.gpu
 
@@ -37,35 +37,6 @@ CFGS = {
 def _need_gpu():
     if not torch.cuda.is_available():
         pytest.fail("gpu tests need a HIP device")
-
-
-def _argsort(v):
-    v = np.ascontiguousarray(v, dtype=np.float32)
-    out = np.zeros(v.size, np.int64)
-    O.lib().oracle_argsort_f32(O._p(v), v.size, O._p(out))
-    return out
-
-
-def literal_act(obs, P, V, policy):
-    """firstfit.py:21-38 / bestfit.py:21-40 over one f32 observation."""
-    obs = np.asarray(obs, dtype=np.float32)
-    placement = obs[:V].astype(np.int64)  # convert_obs_to_dict's astype(int), utils.py:41
-    vm_cpu, vm_mem = obs[V:2 * V], obs[2 * V:3 * V]
-    cpu, mem = obs[3 * V:3 * V + P].copy(), obs[3 * V + P:].copy()
-    action = placement.copy()
-    one = np.float32(1)
-    for v in range(V):
-        if placement[v] != P:
-            continue
-        order = range(P) if policy == "firstfit" else np.flip(_argsort(cpu + mem))
-        for p in order:
-            if cpu[p] + vm_cpu[v] <= one and mem[p] + vm_mem[v] <= one:
-                action[v] = p
-                cpu[p] += vm_cpu[v]
-                if policy == "bestfit":
-                    mem[p] += vm_mem[v]
-                break
-    return action
 
 
 def _edit(obs, P, V, g, ties):

@@ -210,3 +210,149 @@ def test_rollout_timed_passes_repeat_the_same_window():
             if s >= 25:
                 tot += r
         assert tot == rs[0, i]
+
+
+# ------------------------------- the models of branch / set_state / set_workload
+_API_CFG = dict(pms=6, vms=40, arrival_rate=2.0, service_length=9, training_steps=60,
+                eval_steps=100000, seed=5, reward_function="kl", sequence="uniform",
+                cap_target_util=True, beta=0.3, allow_null_action=True)
+
+
+def _random_ext(g, e):
+    a = e.state()[0].copy()
+    draw = g.random(e.V) < 0.5
+    a[draw] = g.integers(0, e.P + 2, int(draw.sum()))
+    return a
+
+
+def _drive(e, driver, g):
+    return e.firstfit() if driver == "firstfit" else e.bestfit() if driver == "bestfit" \
+        else _random_ext(g, e)
+
+
+def _same_env(a, b, what):
+    for x, y in zip(a.state(), b.state()):
+        assert np.array_equal(x, y), what
+    for x, y in zip(a.counters(), b.counters()):
+        assert np.array_equal(x.view(np.uint64), y.view(np.uint64)), what
+    assert a.rank() == b.rank(), what
+
+
+def _lockstep(a, b, driver, steps, seed=1):
+    """a and b step under the same driver and must return the same values, bit for bit."""
+    ga, gb = np.random.default_rng(seed), np.random.default_rng(seed)
+    for t in range(steps):
+        xa, xb = _drive(a, driver, ga), _drive(b, driver, gb)
+        assert np.array_equal(xa, xb), (driver, t)
+        (oa, ra, da, va), (ob, rb, db, vb) = a.step(xa), b.step(xb)
+        assert np.array_equal(oa, ob) and np.array_equal(va, vb) and da == db, (driver, t)
+        assert np.float64(ra).view(np.uint64) == np.float64(rb).view(np.uint64), (driver, t)
+        _same_env(a, b, (driver, t))
+
+
+@pytest.mark.parametrize("driver", ["firstfit", "bestfit", "ext"])
+def test_assigned_env_continues_as_its_source(driver):
+    """assign copies the whole state, the streams and the sequence bases (a
+    reset(None) inside the 100 steps rewinds both alike), not the eval mode."""
+    src = O.OracleEnv(_API_CFG)
+    g = np.random.default_rng(2)
+    for _ in range(37):
+        src.step(_drive(src, driver, g))
+    dst = O.OracleEnv(dict(_API_CFG, seed=99))
+    dst.eval(True)
+    for _ in range(5):
+        dst.step(dst.firstfit())
+    dst.assign(src)
+    _same_env(src, dst, "assigned")
+    # eval mode stayed dst's own: at timestep 60 the source is done, the copy is not
+    a, b = O.OracleEnv(_API_CFG), O.OracleEnv(_API_CFG)
+    a.assign(src)
+    b.assign(dst)
+    b.eval(True)
+    for t in range(38, 61):
+        da, db = a.step(a.firstfit())[2], b.step(b.firstfit())[2]
+        assert (da, db) == (t >= 60, False), t
+    src.eval(True)  # both in eval mode from here: no episode end decides anything
+    for k in range(2):
+        _lockstep(src, dst, driver, 50, seed=3 + k)
+        src.reset(None)
+        dst.reset(None)
+
+
+@pytest.mark.parametrize("loads", [True, False])
+def test_set_state_of_the_exported_state_is_an_identity(loads):
+    """state(), counters and totals imported back: the env continues as its
+    twin, with the loads verbatim; as sums of hundredths when no step has yet
+    left rounding residue in them (a fresh placement of every VM)."""
+    a, b = O.OracleEnv(_API_CFG), O.OracleEnv(_API_CFG)
+    g = np.random.default_rng(4)
+    for e in (a, b):
+        ge = np.random.default_rng(4)
+        for _ in range(30 if loads else 1):
+            e.step(_random_ext(ge, e) if loads else e.firstfit())
+    if not loads:  # one more step places the first arrivals: every load is one exact sum
+        for e in (a, b):
+            e.step(e.firstfit())
+    pl, vc, vm, c, m, rem = b.state()
+    ctr, st = b.counters()
+    if not loads:
+        from tests import state_literal as SL
+        s = SL._sums(dict(vm_placement=pl, vm_cpu=vc, vm_memory=vm), b.P)
+        assert np.array_equal(np.array(s, np.float64) / 100.0, np.r_[c, m]) and sum(s) > 0
+    # poison first: set_state must write every array and recompute the stats
+    z = np.zeros(b.V)
+    b.set_state(np.full(b.V, b.P + 1), z, z, z.astype(np.int64), counters=np.arange(6) + 1,
+                totals=[1.0, 2.0])
+    assert b.counters()[0].tolist() == [1, 2, 3, 4, 5, 6] and b.counters()[1].tolist() == [0, 0, 0, 1, 2]
+    b.set_state(pl, vc, vm, rem, c if loads else None, m if loads else None, ctr, st[3:5])
+    _same_env(a, b, "imported")
+    _lockstep(a, b, "ext", 100)
+    # without counters and totals the env keeps its own
+    pl, vc, vm, c, m, rem = b.state()
+    before = b.counters()
+    b.set_state(pl, vc, vm, rem, c, m)
+    assert all(np.array_equal(x, y) for x, y in zip(before, b.counters()))
+    del g
+
+
+def test_reseeded_env_draws_from_the_fresh_streams():
+    """reseed(s) on an env in mid-run: its state stays, and what it then draws
+    (arrivals, sizes, runtimes) is what the streams of a fresh reset(s) env
+    give; a later reset(None) rewinds to that seed's second sequence."""
+    s = (1 << 33) + 7
+    cfg = dict(_API_CFG, vms=400, pms=40)  # room for every arrival: draws are not cut by drops
+    a = O.OracleEnv(cfg)
+    for _ in range(20):
+        a.step(a.firstfit())
+    before = a.state()
+    ctr0 = a.counters()[0].copy()
+    a.reseed(s)
+    assert all(np.array_equal(x, y) for x, y in zip(before, a.state()))
+    fresh = O.OracleEnv(dict(cfg, seed=s))
+    for t in range(25):
+        pa, pf = a.state()[0], fresh.state()[0]
+        a.step(pa)  # nothing is placed: every accepted VM stays where its draw put it
+        fresh.step(pf)
+        na, nf = a.state(), fresh.state()
+        # (a slot freed by a finisher is refilled in the same step)
+        new_a = np.flatnonzero((pa != a.P) & (na[0] == a.P))
+        new_f = np.flatnonzero((pf != a.P) & (nf[0] == a.P))
+        assert new_a.size == new_f.size, t
+        assert a.counters()[0][0] - ctr0[0] == fresh.counters()[0][0], t
+        for k in (1, 2, 5):
+            assert np.array_equal(na[k][new_a], nf[k][new_f]), (t, k)
+    assert fresh.counters()[0][0] > 30
+    a.reset(None)
+    fresh.reset(None)
+    _lockstep(a, fresh, "firstfit", 30)
+
+
+def test_set_workload_mid_run_equals_an_env_created_with_it():
+    a = O.OracleEnv(_API_CFG)
+    for _ in range(25):
+        a.step(a.bestfit())
+    for lam, L in ((11.0, 3.0), (0.0, 5.0), (0.7, 40.0)):
+        b = O.OracleEnv(dict(_API_CFG, arrival_rate=lam, service_length=L, seed=77))
+        b.assign(a)
+        a.set_workload(lam, L)
+        _lockstep(a, b, "bestfit", 40)
