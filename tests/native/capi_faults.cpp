@@ -6,18 +6,26 @@
 // gfx950 objects. Every check prints a line and the program exits non-zero
 // on the first mismatch; the sanitizers abort on the first report.
 //
-//   without a device (the build container): every entry point rejects null
-//   handles / arguments with VMP_EINVAL; vmp_create rejects each invalid
-//   config field (env.py:156's unknown reward, an unknown sequence, P / V
-//   out of range, negative rates and seeds, n_env <= 0) before touching the
-//   device, and a valid config fails cleanly with VMP_EDEVICE;
+//   without a device (the build container): every function of include/vmp.h
+//   that takes a handle rejects a null one with VMP_EINVAL (the workload, trace,
+//   request-log, series, snapshot / restore, branch, set_state and vmp_debug_*
+//   families included); vmp_create rejects each invalid config field
+//   (env.py:156's unknown reward, an unknown sequence, P / V out of range,
+//   negative rates and seeds, n_env <= 0) before touching the device, and a
+//   valid config fails cleanly with VMP_EDEVICE;
 //   with a device (`capi_faults --device`, the GPU box): for every n, the
 //   n-th device allocation of vmp_create / vmp_record_enable / vmp_mask_bool
 //   fails (vmp_debug_fail_alloc) and the call returns VMP_EOOM with nothing
 //   leaked (host: LeakSanitizer; device: the library's live-allocation count,
-//   vmp_debug_live_allocs, back to its value before the call), the
-//   handle stays usable after a failed vmp_record_enable, and a full create /
-//   step / record / destroy cycle runs clean.
+//   vmp_debug_live_allocs, back to its value before the call); the same
+//   sweep for vmp_reqlog_enable (capacity 50: 6 allocations, 4 with the
+//   recorder on, whose scratch it shares) and vmp_series_enable (capacity 20,
+//   stride 2: 4 allocations with PM rows, 3 without), each once with the
+//   recorder off and once with it on, the call one past the last failure point
+//   succeeding and "off" returning the live count to its start; the handle
+//   stays usable after the failed calls, and a full create / 20 BestFit steps
+//   with all three observers on / one read of each / destroy cycle runs clean
+//   and ends at zero live allocations.
 #include <hip/hip_runtime.h>
 #include <sanitizer/lsan_interface.h>
 #include <unistd.h>
@@ -92,7 +100,7 @@ static void argument_checks() {
   }
   seeds[5] = -3;
   expect_einval(vmp_create(&c, 8, seeds.data(), 0, &h), "negative seed");
-  // every entry point on a null handle
+  // every function that takes a handle, on a null one
   int32_t i32[4];
   float f[4];
   double d[4];
@@ -115,6 +123,37 @@ static void argument_checks() {
   expect_einval(vmp_set_stream(nullptr, nullptr), "set_stream null handle");
   expect_einval(vmp_record_enable(nullptr, 1), "record_enable null handle");
   expect_einval(vmp_record_read(nullptr, u32, d), "record_read null handle");
+  expect_einval(vmp_step_mask(nullptr, i32, f, d, u8, u8, u32), "step_mask null handle");
+  expect_einval(vmp_get_state(nullptr, i64, d, d, d, d, i64), "get_state null handle");
+  expect_einval(vmp_dims(nullptr, i32, i32, i32, i32, i32), "dims null handle");
+  expect_einval(vmp_set_workload(nullptr, d, d), "set_workload null handle");
+  expect_einval(vmp_get_workload(nullptr, d, d), "get_workload null handle");
+  int64_t offs[2] = {0, 0};
+  vmp_trace tr;
+  std::memset(&tr, 0, sizeof(tr));
+  tr.steps = 1;
+  tr.offs = offs;
+  expect_einval(vmp_set_trace(nullptr, 1, &tr, nullptr), "set_trace null handle");
+  expect_einval(vmp_clear_trace(nullptr), "clear_trace null handle");
+  expect_einval(vmp_trace_info(nullptr, i32, i32, i64, i64), "trace_info null handle");
+  expect_einval(vmp_reqlog_enable(nullptr, 50), "reqlog_enable null handle");
+  expect_einval(vmp_reqlog_info(nullptr, i64), "reqlog_info null handle");
+  expect_einval(vmp_reqlog_read(nullptr, i32, i64), "reqlog_read null handle");
+  expect_einval(vmp_series_enable(nullptr, 20, 2, 1), "series_enable null handle");
+  expect_einval(vmp_series_info(nullptr, i64, i32, i32), "series_info null handle");
+  expect_einval(vmp_series_read(nullptr, d, f, i64), "series_read null handle");
+  alignas(16) uint8_t snap[16];
+  expect_einval(vmp_snapshot_bytes(nullptr, i64), "snapshot_bytes null handle");
+  expect_einval(vmp_snapshot(nullptr, snap), "snapshot null handle");
+  expect_einval(vmp_restore(nullptr, snap), "restore null handle");
+  expect_einval(vmp_branch(nullptr, nullptr, i32, i64), "branch null handles");
+  expect_einval(vmp_set_state(nullptr, u8, i64, d, d, i64, d, d, i64, d, i64, u8),
+                "set_state null handle");
+  uint64_t u64[4];
+  expect_einval(vmp_debug_stamps(nullptr, u64), "debug_stamps null handle");
+  expect_einval(vmp_debug_occupancy(nullptr, i32, i32), "debug_occupancy null handle");
+  expect_einval(vmp_debug_launch_order(nullptr, 0), "debug_launch_order null handle");
+  expect_einval(vmp_debug_launch_map(nullptr, i32, u8), "debug_launch_map null handle");
   expect_einval(vmp_debug_fail_alloc(-1), "fail_alloc negative");
   CHECK(vmp_destroy(nullptr) == VMP_OK, "destroy null");
   std::printf("ok  argument checks\n");
@@ -150,6 +189,43 @@ static int create_sweep(const vmp_config &c, std::vector<int64_t> &seeds) {
   return n_fail;
 }
 
+// One observer's enable call under injected out-of-memory: for every n up to its `count`
+// allocations the n-th fails, the call returns VMP_EOOM and the live-allocation count is
+// back at its value before the call; with n one past the count it succeeds, having made
+// exactly `count`; `off` then returns the live count to where it started.
+template <class On, class Off>
+static void enable_sweep(const char *what, int count, On on, Off off) {
+  const int64_t live = vmp_debug_live_allocs();
+  for (int n = 1; n <= count; n++) {
+    vmp_debug_fail_alloc(n);
+    const int rc = on();
+    vmp_debug_fail_alloc(0);
+    CHECK(rc == VMP_EOOM, what);
+    CHECK(vmp_debug_live_allocs() == live, what);
+  }
+  vmp_debug_fail_alloc(count + 1);
+  const int rc = on();
+  vmp_debug_fail_alloc(0);
+  CHECK(rc == VMP_OK, what);
+  CHECK(vmp_debug_live_allocs() == live + count, what);
+  CHECK(off() == VMP_OK, what);
+  CHECK(vmp_debug_live_allocs() == live, what);
+  std::printf("ok  %s: %d failure points, then on and off; live device allocations %lld\n", what,
+              count, (long long)live);
+}
+
+// The request log (capacity 50) and the time series (capacity 20, stride 2, with and
+// without PM rows) on handle h; `log_allocs` is 6, or 4 where the recorder is on and
+// the log shares its scratch actions and validity flags
+static void observer_sweeps(vmp_handle *h, int log_allocs) {
+  enable_sweep("reqlog_enable", log_allocs, [h] { return vmp_reqlog_enable(h, 50); },
+               [h] { return vmp_reqlog_enable(h, 0); });
+  enable_sweep("series_enable with PM rows", 4, [h] { return vmp_series_enable(h, 20, 2, 1); },
+               [h] { return vmp_series_enable(h, 0, 1, 0); });
+  enable_sweep("series_enable without PM rows", 3, [h] { return vmp_series_enable(h, 20, 2, 0); },
+               [h] { return vmp_series_enable(h, 0, 1, 0); });
+}
+
 static void device_faults() {
   vmp_config c = base_cfg();
   // large enough that a leaked buffer shows in the free memory (vm words
@@ -173,6 +249,7 @@ static void device_faults() {
   CHECK(vmp_debug_live_allocs() == live0 && live0 == 0, "device allocations back to none");
   // record_enable / mask_bool on a live handle
   CHECK(vmp_create(&c, 64, seeds.data(), 0, &h) == VMP_OK, "create");
+  observer_sweeps(h, 6);  // the recorder is off
   for (int n = 1; n <= 9; n++) {  // warm: the recorder's first allocations
     vmp_debug_fail_alloc(n);
     (void)vmp_record_enable(h, 1);
@@ -190,10 +267,20 @@ static void device_faults() {
   std::printf("ok  record_enable: 9 failure points; free device memory %zu -> %zu bytes\n",
               with_handle, free_mem());
   CHECK(vmp_record_enable(h, 1) == VMP_OK, "record_enable after the failures");
-  float *obs = nullptr;
-  double *rew = nullptr, *sums = nullptr;
+  observer_sweeps(h, 4);  // the recorder is on
+  CHECK(vmp_reqlog_enable(h, 50) == VMP_OK, "reqlog_enable");
+  CHECK(vmp_series_enable(h, 20, 2, 1) == VMP_OK, "series_enable");
+  float *obs = nullptr, *sr_pm = nullptr;
+  double *rew = nullptr, *sums = nullptr, *sr_rows = nullptr;
   uint8_t *done = nullptr, *mask = nullptr;
   uint32_t *hist = nullptr;
+  int32_t *rq_rows = nullptr;
+  int64_t *rq_meta = nullptr, *sr_meta = nullptr;
+  CHECK(hipMalloc(&rq_rows, sizeof(int32_t) * 64 * 50 * VMP_RQ_NF) == hipSuccess, "rq_rows");
+  CHECK(hipMalloc(&rq_meta, sizeof(int64_t) * 64 * VMP_RQ_NMETA) == hipSuccess, "rq_meta");
+  CHECK(hipMalloc(&sr_rows, sizeof(double) * 64 * 20 * VMP_SR_NF) == hipSuccess, "sr_rows");
+  CHECK(hipMalloc(&sr_pm, sizeof(float) * 64 * 20 * 2 * 100) == hipSuccess, "sr_pm");
+  CHECK(hipMalloc(&sr_meta, sizeof(int64_t) * 64 * VMP_SR_NMETA) == hipSuccess, "sr_meta");
   CHECK(hipMalloc(&obs, sizeof(float) * 64 * (3 * 300 + 2 * 100)) == hipSuccess, "obs");
   CHECK(hipMalloc(&rew, sizeof(double) * 64) == hipSuccess, "rew");
   CHECK(hipMalloc(&done, 64) == hipSuccess, "done");
@@ -204,6 +291,8 @@ static void device_faults() {
     CHECK(vmp_heuristic_step(h, VMP_POLICY_BESTFIT, nullptr, obs, rew, done, nullptr) == VMP_OK,
           "heuristic_step");
   CHECK(vmp_record_read(h, hist, sums) == VMP_OK, "record_read");
+  CHECK(vmp_reqlog_read(h, rq_rows, rq_meta) == VMP_OK, "reqlog_read");
+  CHECK(vmp_series_read(h, sr_rows, sr_pm, sr_meta) == VMP_OK, "series_read");
   const int64_t live_r = vmp_debug_live_allocs();
   vmp_debug_fail_alloc(1);
   CHECK(vmp_mask_bool(h, mask) == VMP_EOOM, "mask_bool under injected OOM");
@@ -219,6 +308,11 @@ static void device_faults() {
   (void)hipFree(mask);
   (void)hipFree(hist);
   (void)hipFree(sums);
+  (void)hipFree(rq_rows);
+  (void)hipFree(rq_meta);
+  (void)hipFree(sr_rows);
+  (void)hipFree(sr_pm);
+  (void)hipFree(sr_meta);
   std::printf("ok  device failure paths (%d vmp_create failure points)\n", n_fail);
 }
 

@@ -4,8 +4,14 @@ tests/test_sanitizers_cpu.py / `make -C vm-placement-migration-gym_amd
 sanitize`): for every allocation of vmp_create the injected out-of-memory
 returns VMP_EOOM with no host leak (LeakSanitizer) and the device memory back
 to its starting level; vmp_record_enable failing at each of its 9
-allocations leaves the handle usable; vmp_mask_bool likewise; a full
-create / BestFit steps / record / destroy cycle runs clean. Host-only
+allocations leaves the handle usable; vmp_reqlog_enable (capacity 50: 6
+allocations, 4 with the recorder on) and vmp_series_enable (capacity 20,
+stride 2: 4 allocations with PM rows, 3 without) get the same sweep, once
+with the recorder off and once with it on: VMP_EOOM and the live-allocation
+count back at its value before the call at every failure point, success one
+past the last, and "off" back at the start; vmp_mask_bool likewise; a full
+create / BestFit steps with all three observers on / one read of each /
+destroy cycle runs clean and ends at zero live allocations. Host-only
 instrumentation: the kernels are the normal gfx950 objects."""
 import os
 import subprocess

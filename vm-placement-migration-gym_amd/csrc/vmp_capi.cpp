@@ -1,6 +1,7 @@
 // vmp_capi.cpp — extern "C" entry points of libvmp.so (declared in include/vmp.h).
 // Argument checks, device allocation and kernel dispatch on the handle's stream
-// (error text, counted allocations, Poisson setup: vmp_host.h; LDS carve: vmp_carve.h).
+// (error text, counted allocations, Poisson setup: vmp_host.h; LDS carve: vmp_carve.h;
+// the recorder, request log and time series behind a step: vmp_observers.h).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -16,9 +17,7 @@
 #include "vmp_kernels.h"
 #include "vmp_launch_order.h"
 #include "vmp_layout.h"
-#include "vmp_record.h"
-#include "vmp_reqlog.h"
-#include "vmp_series.h"
+#include "vmp_observers.h"
 #include "vmp_state.h"
 #include "vmp_trace.h"
 
@@ -47,21 +46,7 @@ struct vmp_handle {
   uint64_t *jump_dev;
   uint8_t *bigscr;  // k_env_big's HBM spill of the accepted / existing VM sizes
   bool big;  // k_env_big (V > 1024, or VMP_BIG_KERNEL=1)
-  // eval-mode Record metrics (vmp_record.hip), allocated by vmp_record_enable
-  bool rec_on;
-  RecArgs rec;
-  int32_t *rec_act;   // scratch action / validity / reward when the caller passes none
-  uint8_t *rec_valid;
-  double *rec_reward;
-  // per-request outcome log (vmp_reqlog.hip), allocated by vmp_reqlog_enable; with the
-  // recorder on as well the two share rec_act / rec_valid
-  bool rq_on;
-  ReqArgs rq;
-  // per-step time series (vmp_series.hip), allocated by vmp_series_enable; it steps on
-  // the reward alone: sr_reward where the caller passes no buffer
-  bool sr_on;
-  SerArgs sr;
-  double *sr_reward;
+  Observers ob;  // recorder, request log, time series (vmp_observers.h)
   // per-env workload (vmp_set_workload); all null / 0 for a handle never given one
   double *wl;           // host f64 [N][2]: arrival_rate, service_length of every env
   PoisConst *wl_rec;    // host mirror of pois_env
@@ -83,11 +68,8 @@ struct vmp_handle {
   // two flag buffers lie behind hdr. None of it is part of a snapshot.
   uint32_t lo_count;
   int32_t lo_mode, lo_div;
-  // vmp_branch: the staging copy of hdr | pm | vmw for dst == src, and the mask of
-  // the overwritten envs that restarts the observers (vmp_set_state's too); each
-  // allocated on first use
+  // vmp_branch: the staging copy of hdr | pm | vmw for dst == src, allocated on first use
   uint8_t *br_stage;
-  uint8_t *br_mask;
 };
 
 namespace {
@@ -154,64 +136,9 @@ void refresh_params(vmp_handle *h) {
   h->prm.limit = h->eval_mode ? h->cfg.eval_steps : h->cfg.training_steps;
 }
 
-// the scratch action / validity buffers the recorder and the request log step on
-void scratch_free(vmp_handle *h) {
-  dev_free(h->rec_act);
-  dev_free(h->rec_valid);
-  h->rec_act = nullptr;
-  h->rec_valid = nullptr;
-}
-
-// (re)start the recorder of the envs flagged in env_mask (device, null = all)
-int record_init(vmp_handle *h, const uint8_t *env_mask) {
-  size_t n = (size_t)h->N * h->V;
-  if ((size_t)h->N * 2 * VMP_REC_BINS > n) n = (size_t)h->N * 2 * VMP_REC_BINS;
-  if ((size_t)h->N * VMP_NREC > n) n = (size_t)h->N * VMP_NREC;
-  hipLaunchKernelGGL(k_record_init, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream,
-                     h->prm, h->rec, env_mask);
-  return launched();
-}
-
-// (re)start the request log of the envs flagged in env_mask (device, null = all)
-int reqlog_init(vmp_handle *h, const uint8_t *env_mask) {
-  const int64_t rows = h->rq.cap * VMP_RQ_NF;
-  const int64_t n = (int64_t)h->N * (rows > h->V ? rows : h->V);
-  const int64_t blocks = (n + 255) / 256;
-  hipLaunchKernelGGL(k_reqlog_init, dim3((unsigned)(blocks < (1 << 20) ? blocks : (1 << 20))), dim3(256),
-                     0, h->stream, h->prm, h->rq, env_mask);
-  return launched();
-}
-
-// (re)start the time series of the envs flagged in env_mask (device, null = all)
-int series_init(vmp_handle *h, const uint8_t *env_mask) {
-  const int64_t per = h->sr.pm && 2 * (int64_t)h->P > VMP_SR_NF ? 2 * (int64_t)h->P : VMP_SR_NF;
-  const int64_t n = (int64_t)h->N * h->sr.cap * per;
-  const int64_t blocks = (n + 255) / 256;
-  hipLaunchKernelGGL(k_series_init, dim3((unsigned)(blocks < (1 << 20) ? blocks : (1 << 20))), dim3(256),
-                     0, h->stream, h->prm, h->sr, env_mask);
-  return launched();
-}
-
-// k_series where its static LDS holds the env, else k_series_lds on a private carve
-bool series_wave(const vmp_handle *h) { return h->V <= kMaxVPT * kWaveSize && h->P <= 1024; }
-// k_series_lds's dynamic LDS: carve_target_means' regions in q, then the used-PM bitmap
-size_t series_lds(const vmp_handle *h, EnvParams &q, int32_t *off_used) {
-  q = h->prm;
-  *off_used = (int32_t)align16((int64_t)carve_target_means(q));
-  return (size_t)*off_used + sizeof(uint64_t) * (size_t)((h->P + 63) / 64);
-}
-
-int launch_series(vmp_handle *h, const double *reward) {
-  SerArgs a = h->sr;
-  a.reward = reward;
-  if (series_wave(h)) {
-    hipLaunchKernelGGL(k_series, dim3((h->N + 3) / 4), dim3(256), 0, h->stream, h->prm, a);
-    return launched();
-  }
-  EnvParams q;
-  const size_t lds = series_lds(h, q, &a.off_used);
-  hipLaunchKernelGGL(k_series_lds, dim3(h->N), dim3(64), lds, h->stream, q, a);
-  return launched();
+// One step and the observers that are on behind it (Observers::step)
+int step_observed(vmp_handle *h, const StepOut &o) {
+  return h->ob.step(h->prm, h->stream, o, [h](const StepOut &x) { return launch_env(h, x); });
 }
 
 int check_policy(int32_t policy) {
@@ -351,7 +278,7 @@ int vmp_destroy(vmp_handle *h) {
   for (void *q : {(void *)h->vmw, (void *)h->pm, (void *)h->hdr, (void *)h->lg_arr, (void *)h->lg_svc,
                   (void *)h->scratch_bits, (void *)h->pois_dev, (void *)h->jump_dev, (void *)h->bigscr,
                   (void *)h->stamps, (void *)h->pois_env, (void *)h->lg_shared, (void *)h->tr_tab,
-                  (void *)h->tr_data, (void *)h->br_stage, (void *)h->br_mask})
+                  (void *)h->tr_data, (void *)h->br_stage, (void *)h->ob.mask})
     dev_free(q);
   std::free(h->wl);
   std::free(h->wl_rec);
@@ -414,9 +341,7 @@ int vmp_set_workload(vmp_handle *h, const double *arrival_rate, const double *se
   }
   if (rc == VMP_OK && first) {
     const hipError_t e = dev_malloc(&dev_new, sizeof(PoisConst) * 2 * N);
-    if (e != hipSuccess)
-      rc = fail(e == hipErrorOutOfMemory ? VMP_EOOM : VMP_EDEVICE,
-                std::string("vmp_set_workload: ") + hipGetErrorString(e));
+    if (e != hipSuccess) rc = fail_hip("vmp_set_workload: ", e);
   }
   if (rc == VMP_OK) {
     for (PoisConst &c : rec)
@@ -500,9 +425,7 @@ int vmp_set_trace(vmp_handle *h, int32_t n_traces, const vmp_trace *traces,
   if (rc == VMP_OK) {
     hipError_t e = dev_malloc(&data_new, sizeof(uint64_t) * words);
     if (e == hipSuccess && first) e = dev_malloc(&tab_new, sizeof(TraceDesc) * N);
-    if (e != hipSuccess)
-      rc = fail(e == hipErrorOutOfMemory ? VMP_EOOM : VMP_EDEVICE,
-                std::string("vmp_set_trace: ") + hipGetErrorString(e));
+    if (e != hipSuccess) rc = fail_hip("vmp_set_trace: ", e);
   }
   if (rc == VMP_OK) {
     for (size_t e = 0; e < N; e++) {
@@ -619,50 +542,7 @@ int vmp_reset(vmp_handle *h, const int64_t *seeds, const uint8_t *env_mask, floa
   dim3 grid((h->N + kWavesPerBlock - 1) / kWavesPerBlock), block(64 * kWavesPerBlock);
   hipLaunchKernelGGL(k_reset, grid, block, 0, h->stream, h->prm, seeds, env_mask, obs);
   if (const int rc = launched()) return rc;
-  if (h->rec_on)  // the recorder of the envs just reset restarts
-    if (const int rc = record_init(h, env_mask)) return rc;
-  if (h->rq_on)  // ... and so does their log
-    if (const int rc = reqlog_init(h, env_mask)) return rc;
-  return h->sr_on ? series_init(h, env_mask) : VMP_OK;  // ... and their time series
-}
-
-// One step; with recording on, the recorder (vmp_record.hip) after it, on the
-// handle's scratch action / validity / reward where the caller passes none;
-// with the request log on, its kernel (vmp_reqlog.hip) likewise
-static int step_observed(vmp_handle *h, StepOut o);
-// ... and behind them the time series (vmp_series.hip), which needs the step's reward
-// only: no actions or validity flags are asked for on its account, so a handle with
-// nothing else on keeps the step kernel's idle path
-static int step_recorded(vmp_handle *h, StepOut o) {
-  if (!h->sr_on) return step_observed(h, o);
-  if (!o.reward) o.reward = h->sr_reward;
-  if (const int rc = step_observed(h, o)) return rc;
-  return launch_series(h, o.reward);
-}
-
-static int step_observed(vmp_handle *h, StepOut o) {
-  if (!h->rec_on && !h->rq_on) return launch_env(h, o);
-  if (!o.actions && !o.act_out) o.act_out = h->rec_act;
-  if (h->rec_on && !o.reward) o.reward = h->rec_reward;
-  if (!o.valid) o.valid = h->rec_valid;
-  if (const int rc = launch_env(h, o)) return rc;
-  if (h->rec_on) {
-    RecArgs r = h->rec;
-    r.act = o.actions ? o.actions : o.act_out;
-    r.valid = o.valid;
-    r.reward = o.reward;
-    const size_t lds = (size_t)4 * ((h->P + 63) / 64) * sizeof(unsigned long long);
-    hipLaunchKernelGGL(k_record, dim3((h->N + 3) / 4), dim3(256), lds, h->stream, h->prm, r);
-    if (const int rc = launched()) return rc;
-  }
-  if (h->rq_on) {
-    ReqArgs q = h->rq;
-    q.act = o.actions ? o.actions : o.act_out;
-    q.valid = o.valid;
-    hipLaunchKernelGGL(k_reqlog, dim3((h->N + 3) / 4), dim3(256), 0, h->stream, h->prm, q);
-    return launched();
-  }
-  return VMP_OK;
+  return h->ob.restart(h->prm, h->stream, env_mask);  // the observers of the envs just reset
 }
 
 int vmp_step(vmp_handle *h, const int32_t *actions, float *obs, double *reward, uint8_t *done,
@@ -681,7 +561,7 @@ int vmp_step_mask(vmp_handle *h, const int32_t *actions, float *obs, double *rew
   o.valid = valid;
   o.mask_bits = next_mask_bits;  // written from the post-step state, as vmp_mask would
   o.k_steps = 1;
-  return step_recorded(h, o);
+  return step_observed(h, o);
 }
 
 int vmp_heuristic_act(vmp_handle *h, int32_t policy, int32_t *actions) {
@@ -719,7 +599,7 @@ static int heuristic_step_impl(vmp_handle *h, int32_t policy, int32_t *actions_o
   o.done_count = done_count;
   o.valid = valid;
   o.k_steps = 1;
-  return step_recorded(h, o);
+  return step_observed(h, o);
 }
 
 int vmp_heuristic_step(vmp_handle *h, int32_t policy, int32_t *actions_out, float *obs,
@@ -731,7 +611,7 @@ int vmp_rollout_heuristic(vmp_handle *h, int32_t policy, int32_t k_steps, double
                           int64_t *done_count) {
   if (!h || k_steps < 1) return fail(VMP_EINVAL, "null handle or k_steps < 1");
   if (const int rc = check_policy(policy)) return rc;
-  if (h->rec_on || h->rq_on || h->sr_on) {  // observed: one step per launch, the observers after each
+  if (h->ob.any()) {  // observed: one step per launch, the observers after each
     for (int32_t k = 0; k < k_steps; k++) {
       int rc = heuristic_step_impl(h, policy, nullptr, nullptr,
                                    rewards ? rewards + (int64_t)k * h->N : nullptr, nullptr,
@@ -753,195 +633,45 @@ int vmp_rollout_heuristic(vmp_handle *h, int32_t policy, int32_t k_steps, double
   return VMP_OK;
 }
 
+// ---- the observers: Record metrics, per-request outcome log, per-step time series ----
 int vmp_record_enable(vmp_handle *h, int32_t on) {
   if (!h) return fail(VMP_EINVAL, "null handle");
-  if (!on) {
-    if (h->rec_on) (void)hipStreamSynchronize(h->stream);
-    for (void *q : {(void *)h->rec.prev, (void *)h->rec.life_n, (void *)h->rec.alloc, (void *)h->rec.waits,
-                    (void *)h->rec.hist, (void *)h->rec.sums, (void *)h->rec_reward})
-      dev_free(q);
-    std::memset(&h->rec, 0, sizeof(h->rec));
-    h->rec_reward = nullptr;
-    h->rec_on = false;
-    if (!h->rq_on) scratch_free(h);  // the request log steps on the same scratch
-    return VMP_OK;
-  }
-  const size_t nv = (size_t)h->N * h->V;
-  if (!h->rec.prev) {
-    // all or nothing: a partial set would leave null buffers behind a
-    // non-null `prev` for the next call's k_record_init to write through
-    const hipError_t e[9] = {
-        dev_malloc(&h->rec.prev, sizeof(uint16_t) * nv),
-        dev_malloc(&h->rec.life_n, sizeof(uint32_t) * nv),
-        dev_malloc(&h->rec.alloc, sizeof(int32_t) * nv),
-        dev_malloc(&h->rec.waits, sizeof(uint32_t) * nv),
-        dev_malloc(&h->rec.hist, sizeof(uint32_t) * (size_t)h->N * 2 * VMP_REC_BINS),
-        dev_malloc(&h->rec.sums, sizeof(double) * (size_t)h->N * VMP_NREC),
-        h->rec_act ? hipSuccess : dev_malloc(&h->rec_act, sizeof(int32_t) * nv),
-        h->rec_valid ? hipSuccess : dev_malloc(&h->rec_valid, nv),
-        dev_malloc(&h->rec_reward, sizeof(double) * (size_t)h->N)};
-    for (hipError_t x : e)
-      if (x != hipSuccess) {
-        vmp_record_enable(h, 0);
-        return fail(x == hipErrorOutOfMemory ? VMP_EOOM : VMP_EDEVICE,
-                    std::string("vmp_record_enable: ") + hipGetErrorString(x));
-      }
-  }
-  if (const int rc = record_init(h, nullptr)) return rc;
-  h->rec_on = true;
-  return VMP_OK;
-}
-
-// ---- per-request outcome log ----
-int vmp_reqlog_enable(vmp_handle *h, int64_t capacity) {
-  if (!h) return fail(VMP_EINVAL, "null handle");
-  if (capacity < 0) return fail(VMP_EINVAL, "vmp_reqlog_enable: capacity must be >= 0");
-  if (capacity == 0) {
-    if (h->rq_on) (void)hipStreamSynchronize(h->stream);
-    for (void *q : {(void *)h->rq.rows, (void *)h->rq.ids, (void *)h->rq.prev, (void *)h->rq.meta})
-      dev_free(q);
-    std::memset(&h->rq, 0, sizeof(h->rq));
-    h->rq_on = false;
-    if (!h->rec_on) scratch_free(h);
-    return VMP_OK;
-  }
-  ReqlogSizes sz;
-  if (const char *why = reqlog_sizes(h->N, h->V, capacity, &sz)) return fail(VMP_EINVAL, why);
-  // a new set first: on any failure the handle, and a log it had, stay as they were
-  ReqArgs q;
-  std::memset(&q, 0, sizeof(q));
-  q.cap = capacity;
-  int32_t *act_new = nullptr;
-  uint8_t *valid_new = nullptr;
-  const size_t nv = (size_t)h->N * h->V;
-  const hipError_t e[6] = {
-      dev_malloc(&q.rows, sz.rows),
-      dev_malloc(&q.ids, sz.ids),
-      dev_malloc(&q.prev, sz.prev),
-      dev_malloc(&q.meta, sz.meta),
-      h->rec_act ? hipSuccess : dev_malloc(&act_new, sizeof(int32_t) * nv),
-      h->rec_valid ? hipSuccess : dev_malloc(&valid_new, nv)};
-  for (hipError_t x : e)
-    if (x != hipSuccess) {
-      for (void *b : {(void *)q.rows, (void *)q.ids, (void *)q.prev, (void *)q.meta, (void *)act_new,
-                      (void *)valid_new})
-        dev_free(b);
-      return fail(x == hipErrorOutOfMemory ? VMP_EOOM : VMP_EDEVICE,
-                  std::string("vmp_reqlog_enable: ") + hipGetErrorString(x));
-    }
-  if (h->rq_on) {  // queued launches write the log this one replaces
-    (void)hipStreamSynchronize(h->stream);
-    for (void *b : {(void *)h->rq.rows, (void *)h->rq.ids, (void *)h->rq.prev, (void *)h->rq.meta})
-      dev_free(b);
-  }
-  h->rq = q;
-  if (act_new) h->rec_act = act_new;
-  if (valid_new) h->rec_valid = valid_new;
-  h->rq_on = true;
-  return reqlog_init(h, nullptr);
-}
-
-int vmp_reqlog_info(const vmp_handle *h, int64_t *capacity) {
-  if (!h || !capacity) return fail(VMP_EINVAL, "null argument");
-  *capacity = h->rq_on ? h->rq.cap : 0;
-  return VMP_OK;
-}
-
-int vmp_reqlog_read(vmp_handle *h, int32_t *rows, int64_t *meta) {
-  if (!h) return fail(VMP_EINVAL, "null handle");
-  if (!h->rq_on) return fail(VMP_ESTATE, "the request log is not enabled (vmp_reqlog_enable)");
-  ReqlogSizes sz;
-  if (const char *why = reqlog_sizes(h->N, h->V, h->rq.cap, &sz)) return fail(VMP_EINVAL, why);
-  if (rows) {
-    HIP_TRY(hipMemcpyAsync(rows, h->rq.rows, sz.rows, hipMemcpyDeviceToDevice, h->stream));
-    // WAIT_STEPS of the VMs waiting now is kept open on the device: closed in the copy
-    hipLaunchKernelGGL(k_reqlog_close, dim3((h->N + 3) / 4), dim3(256), 0, h->stream, h->prm, h->rq, rows);
-    if (const int rc = launched()) return rc;
-  }
-  if (meta) HIP_TRY(hipMemcpyAsync(meta, h->rq.meta, sz.meta, hipMemcpyDeviceToDevice, h->stream));
-  return VMP_OK;
-}
-
-// ---- per-step time series ----
-int vmp_series_enable(vmp_handle *h, int64_t capacity, int32_t stride, int32_t pm_rows) {
-  if (!h) return fail(VMP_EINVAL, "null handle");
-  if (capacity < 0) return fail(VMP_EINVAL, "vmp_series_enable: capacity must be >= 0");
-  if (capacity == 0) {
-    if (h->sr_on) (void)hipStreamSynchronize(h->stream);
-    for (void *q : {(void *)h->sr.rows, (void *)h->sr.pm, (void *)h->sr.meta, (void *)h->sr_reward})
-      dev_free(q);
-    std::memset(&h->sr, 0, sizeof(h->sr));
-    h->sr_reward = nullptr;
-    h->sr_on = false;
-    return VMP_OK;
-  }
-  SeriesSizes sz;
-  if (const char *why = series_sizes(h->N, h->P, capacity, stride, pm_rows, &sz))
-    return fail(VMP_EINVAL, why);
-  if (!series_wave(h)) {
-    EnvParams q;
-    int32_t off = 0;
-    if (series_lds(h, q, &off) > (size_t)64 * 1024)
-      return fail(VMP_EINVAL, "vmp_series_enable: config too large for the series kernel's LDS");
-  }
-  // a new set first: on any failure the handle, and a series it had, stay as they were
-  SerArgs a;
-  std::memset(&a, 0, sizeof(a));
-  a.cap = capacity;
-  a.stride = stride;
-  double *reward_new = nullptr;
-  const hipError_t e[4] = {
-      dev_malloc(&a.rows, sz.rows),
-      pm_rows ? dev_malloc(&a.pm, sz.pm) : hipSuccess,
-      dev_malloc(&a.meta, sz.meta),
-      h->sr_reward ? hipSuccess : dev_malloc(&reward_new, sz.reward)};
-  for (hipError_t x : e)
-    if (x != hipSuccess) {
-      for (void *b : {(void *)a.rows, (void *)a.pm, (void *)a.meta, (void *)reward_new}) dev_free(b);
-      return fail(x == hipErrorOutOfMemory ? VMP_EOOM : VMP_EDEVICE,
-                  std::string("vmp_series_enable: ") + hipGetErrorString(x));
-    }
-  if (h->sr_on) {  // queued launches write the series this one replaces
-    (void)hipStreamSynchronize(h->stream);
-    for (void *b : {(void *)h->sr.rows, (void *)h->sr.pm, (void *)h->sr.meta}) dev_free(b);
-  }
-  h->sr = a;
-  if (reward_new) h->sr_reward = reward_new;
-  h->sr_on = true;
-  return series_init(h, nullptr);
-}
-
-int vmp_series_info(const vmp_handle *h, int64_t *capacity, int32_t *stride, int32_t *pm_rows) {
-  if (!h) return fail(VMP_EINVAL, "null handle");
-  if (capacity) *capacity = h->sr_on ? h->sr.cap : 0;
-  if (stride) *stride = h->sr_on ? h->sr.stride : 0;
-  if (pm_rows) *pm_rows = h->sr_on && h->sr.pm ? 1 : 0;
-  return VMP_OK;
-}
-
-int vmp_series_read(vmp_handle *h, double *rows, float *pm, int64_t *meta) {
-  if (!h) return fail(VMP_EINVAL, "null handle");
-  if (!h->sr_on) return fail(VMP_ESTATE, "the time series is not enabled (vmp_series_enable)");
-  if (pm && !h->sr.pm) return fail(VMP_ESTATE, "the time series keeps no PM rows (pm_rows)");
-  SeriesSizes sz;
-  if (const char *why = series_sizes(h->N, h->P, h->sr.cap, h->sr.stride, h->sr.pm ? 1 : 0, &sz))
-    return fail(VMP_EINVAL, why);
-  if (rows) HIP_TRY(hipMemcpyAsync(rows, h->sr.rows, sz.rows, hipMemcpyDeviceToDevice, h->stream));
-  if (pm) HIP_TRY(hipMemcpyAsync(pm, h->sr.pm, sz.pm, hipMemcpyDeviceToDevice, h->stream));
-  if (meta) HIP_TRY(hipMemcpyAsync(meta, h->sr.meta, sz.meta, hipMemcpyDeviceToDevice, h->stream));
-  return VMP_OK;
+  return h->ob.record_enable(h->prm, h->stream, on);
 }
 
 int vmp_record_read(vmp_handle *h, uint32_t *hist, double *sums) {
   if (!h || !hist || !sums) return fail(VMP_EINVAL, "null argument");
-  if (!h->rec_on) return fail(VMP_ESTATE, "recording is not enabled (vmp_record_enable)");
-  HIP_TRY(hipMemcpyAsync(hist, h->rec.hist, sizeof(uint32_t) * (size_t)h->N * 2 * VMP_REC_BINS,
-                         hipMemcpyDeviceToDevice, h->stream));
-  HIP_TRY(hipMemcpyAsync(sums, h->rec.sums, sizeof(double) * (size_t)h->N * VMP_NREC,
-                         hipMemcpyDeviceToDevice, h->stream));
-  hipLaunchKernelGGL(k_record_close, dim3((h->N + 3) / 4), dim3(256), 0, h->stream, h->prm,
-                     h->rec, hist, sums);
-  return launched();
+  return h->ob.record_read(h->prm, h->stream, hist, sums);
+}
+
+int vmp_reqlog_enable(vmp_handle *h, int64_t capacity) {
+  if (!h) return fail(VMP_EINVAL, "null handle");
+  return h->ob.reqlog_enable(h->prm, h->stream, capacity);
+}
+
+int vmp_reqlog_info(const vmp_handle *h, int64_t *capacity) {
+  if (!h || !capacity) return fail(VMP_EINVAL, "null argument");
+  return h->ob.reqlog_info(capacity);
+}
+
+int vmp_reqlog_read(vmp_handle *h, int32_t *rows, int64_t *meta) {
+  if (!h) return fail(VMP_EINVAL, "null handle");
+  return h->ob.reqlog_read(h->prm, h->stream, rows, meta);
+}
+
+int vmp_series_enable(vmp_handle *h, int64_t capacity, int32_t stride, int32_t pm_rows) {
+  if (!h) return fail(VMP_EINVAL, "null handle");
+  return h->ob.series_enable(h->prm, h->stream, capacity, stride, pm_rows);
+}
+
+int vmp_series_info(const vmp_handle *h, int64_t *capacity, int32_t *stride, int32_t *pm_rows) {
+  if (!h) return fail(VMP_EINVAL, "null handle");
+  return h->ob.series_info(capacity, stride, pm_rows);
+}
+
+int vmp_series_read(vmp_handle *h, double *rows, float *pm, int64_t *meta) {
+  if (!h) return fail(VMP_EINVAL, "null handle");
+  return h->ob.series_read(h->prm, h->stream, rows, pm, meta);
 }
 
 int vmp_mask(vmp_handle *h, uint32_t *bits) {
@@ -1106,11 +836,8 @@ int vmp_restore(vmp_handle *h, const void *src) {
   HIP_TRY(hipMemcpyAsync(h->hdr, s + l.hdr, l.nh, hipMemcpyDeviceToDevice, h->stream));
   HIP_TRY(hipMemcpyAsync(h->pm, s + l.pm, l.np, hipMemcpyDeviceToDevice, h->stream));
   HIP_TRY(hipMemcpyAsync(h->vmw, s + l.vmw, l.nv, hipMemcpyDeviceToDevice, h->stream));
-  if (h->rec_on)  // the recorder is no part of a snapshot: it restarts from the restored state
-    if (const int rc = record_init(h, nullptr)) return rc;
-  if (h->rq_on)  // nor is the log
-    if (const int rc = reqlog_init(h, nullptr)) return rc;
-  return h->sr_on ? series_init(h, nullptr) : VMP_OK;  // nor is the time series
+  // no observer is part of a snapshot: all restart from the restored state
+  return h->ob.restart(h->prm, h->stream, nullptr);
 }
 
 // ---- branch: env states between handles on the device ----
@@ -1138,19 +865,11 @@ int vmp_branch(vmp_handle *dst, vmp_handle *src, const int32_t *src_of_dst, cons
   const BranchGeom g = branch_geom(dst->P, vm_pitch(dst->V));
   if ((int64_t)dst->N * g.chunks > 0x7fffffffLL) return fail(VMP_EINVAL, "vmp_branch: too many envs for one launch");
   const SnapLayout l(src);  // sizes of src's three arrays
-  const bool observed = dst->rec_on || dst->rq_on || dst->sr_on;
-  if (dst == src && !dst->br_stage) {
-    const hipError_t e = dev_malloc(&dst->br_stage, l.nh + l.np + l.nv);
-    if (e != hipSuccess)
-      return fail(e == hipErrorOutOfMemory ? VMP_EOOM : VMP_EDEVICE,
-                  std::string("vmp_branch staging: ") + hipGetErrorString(e));
-  }
-  if (observed && !dst->br_mask) {
-    const hipError_t e = dev_malloc(&dst->br_mask, (size_t)dst->N);
-    if (e != hipSuccess)
-      return fail(e == hipErrorOutOfMemory ? VMP_EOOM : VMP_EDEVICE,
-                  std::string("vmp_branch mask: ") + hipGetErrorString(e));
-  }
+  if (dst == src && !dst->br_stage)
+    if (const hipError_t e = dev_malloc(&dst->br_stage, l.nh + l.np + l.nv); e != hipSuccess)
+      return fail_hip("vmp_branch staging: ", e);
+  uint8_t *mask = nullptr;  // null with no observer on
+  if (const int rc = dst->ob.restart_mask(dst->prm, "vmp_branch mask: ", &mask)) return rc;
   BranchArgs a;
   std::memset(&a, 0, sizeof(a));
   a.src_hdr = reinterpret_cast<const uint4 *>(src->hdr);
@@ -1170,7 +889,7 @@ int vmp_branch(vmp_handle *dst, vmp_handle *src, const int32_t *src_of_dst, cons
   a.dst_vmw = reinterpret_cast<uint4 *>(dst->vmw);
   a.src_of_dst = src_of_dst;
   a.seeds = seeds;
-  a.mask = observed ? dst->br_mask : nullptr;
+  a.mask = mask;
   a.src_n = src->N;
   a.dst_n = dst->N;
   a.pm_units = (int32_t)g.pm_units;
@@ -1180,11 +899,8 @@ int vmp_branch(vmp_handle *dst, vmp_handle *src, const int32_t *src_of_dst, cons
   hipLaunchKernelGGL(k_branch, dim3((unsigned)((int64_t)dst->N * g.chunks)), dim3(kBranchThreads), 0,
                      dst->stream, a);
   if (const int rc = launched()) return rc;
-  if (dst->rec_on)  // the observers of the overwritten envs restart from the new state
-    if (const int rc = record_init(dst, dst->br_mask)) return rc;
-  if (dst->rq_on)
-    if (const int rc = reqlog_init(dst, dst->br_mask)) return rc;
-  return dst->sr_on ? series_init(dst, dst->br_mask) : VMP_OK;
+  // the observers of the overwritten envs restart from the new state
+  return dst->ob.restart(dst->prm, dst->stream, mask);
 }
 
 // ---- set state: env states from the caller's arrays ----
@@ -1204,13 +920,8 @@ int vmp_set_state(vmp_handle *h, const uint8_t *env_mask, const int64_t *placeme
   c.P = h ? h->P : 1;
   const char *why = nullptr;
   if (const int rc = state_check(&c, &why)) return fail(rc, why);
-  const bool observed = h->rec_on || h->rq_on || h->sr_on;
-  if (observed && !h->br_mask) {
-    const hipError_t e = dev_malloc(&h->br_mask, (size_t)h->N);
-    if (e != hipSuccess)
-      return fail(e == hipErrorOutOfMemory ? VMP_EOOM : VMP_EDEVICE,
-                  std::string("vmp_set_state mask: ") + hipGetErrorString(e));
-  }
+  uint8_t *mask = nullptr;  // null with no observer on
+  if (const int rc = h->ob.restart_mask(h->prm, "vmp_set_state mask: ", &mask)) return rc;
   StateArgs a;
   std::memset(&a, 0, sizeof(a));
   a.hdr = h->hdr, a.pm = h->pm, a.vmw = h->vmw;
@@ -1219,16 +930,13 @@ int vmp_set_state(vmp_handle *h, const uint8_t *env_mask, const int64_t *placeme
   a.cpu = cpu, a.mem = mem;
   a.counters = counters, a.totals = totals, a.seeds = seeds;
   a.status = status;
-  a.imported = observed ? h->br_mask : nullptr;
+  a.imported = mask;
   a.N = h->N, a.P = h->P, a.V = h->V;
   hipLaunchKernelGGL(k_set_state, dim3((unsigned)h->N), dim3(kStateThreads),
                      (size_t)state_lds_bytes(h->P), h->stream, a);
   if (const int rc = launched()) return rc;
-  if (h->rec_on)  // the observers of the imported envs restart from the new state
-    if (const int rc = record_init(h, h->br_mask)) return rc;
-  if (h->rq_on)
-    if (const int rc = reqlog_init(h, h->br_mask)) return rc;
-  return h->sr_on ? series_init(h, h->br_mask) : VMP_OK;
+  // the observers of the imported envs restart from the new state
+  return h->ob.restart(h->prm, h->stream, mask);
 }
 
 int64_t vmp_debug_live_allocs(void) { return g_live.load(); }

@@ -32,12 +32,16 @@ int fail_after(int rc, F cleanup) {
   return fail(rc, msg);
 }
 
-#define HIP_TRY(expr)                                                              \
-  do {                                                                             \
-    hipError_t _e = (expr);                                                        \
-    if (_e != hipSuccess)                                                          \
-      return fail(_e == hipErrorOutOfMemory ? VMP_EOOM : VMP_EDEVICE,              \
-                  std::string(#expr) + ": " + hipGetErrorString(_e));              \
+// fail() for a HIP error: VMP_EOOM if it is out of memory, else VMP_EDEVICE, with the
+// error's text behind `who`
+inline int fail_hip(const char *who, hipError_t e) {
+  return fail(e == hipErrorOutOfMemory ? VMP_EOOM : VMP_EDEVICE, std::string(who) + hipGetErrorString(e));
+}
+
+#define HIP_TRY(expr)                                 \
+  do {                                                \
+    hipError_t _e = (expr);                           \
+    if (_e != hipSuccess) return fail_hip(#expr ": ", _e); \
   } while (0)
 inline int launched() {  // after a kernel launch
   HIP_TRY(hipGetLastError());
